@@ -48,6 +48,12 @@ Also in the line:
   crossover     under `secondary`: the smallest batch for which one hades252_perm_batch call beats the CPU port
                 (one core / all cores) -- the reference's own call shape is ONE permutation per call (README.md:60-61).
 `--workload merkle` times the tree build itself as the step (development; the driver runs the default).
+`--dump-outputs DIR`: after the timed steps, what the last step left in the buffer (the permuted states a caller of the
+hot path receives) is written to DIR as float64 .npy files, at most 64 MB in all: a fixed, seeded sample of the states
+(`states.npy`, every 64-bit limb as its exact low and high 32-bit halves; `state_index.npy`, their global indices) and
+the digest of ALL outputs (`digest.npy`, 4 limbs as halves).  With N > 1 every rank writes its own sample
+(`states_rank<g>.npy`, `state_index_rank<g>.npy`).  The inputs depend on the arguments only, so two builds can be
+compared output for output.  With `--workload merkle`: `root.npy` of the last timed build.
 `--total-perms T` (strong scaling): T permutations IN ALL, rank g owns the contiguous range [g T / N, (g + 1) T / N);
 `--total-perms 1073741824` is BASELINE configs[4] at any N (one device holds all 160 GiB at N = 1), the line then says
 `"scaling": "strong"` and every rank's first launch is checked against the CPU oracle's digest of ALL 2^30 outputs.  The
@@ -151,6 +157,45 @@ def cpu_baseline_and_check(H, torch, device, n_sample: int, kernel: int):
         "all_cores_seconds": n_sample / best["value"],
         "builds": builds,
     }, ok
+
+
+DUMP_BYTES = 64 << 20              # --dump-outputs: all files of one run together
+DUMP_SEED = 0x48616465             # the sample of states a dump holds is fixed: same arguments, same states
+
+
+def u64_halves(a):
+    """uint64 words -> float64 array with a trailing axis (low, high 32-bit half): exact in float64."""
+    import numpy as np
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    return np.stack([a & np.uint64(0xFFFFFFFF), a >> np.uint64(32)], axis=-1).astype(np.float64)
+
+
+def dump_states(out_dir, states, first_perm: int, rank: int, world: int):
+    """--dump-outputs: a seeded sample of this rank's (n, 5, 4) states as they are now, with their global indices."""
+    import numpy as np
+    import torch
+    n = states.shape[0]
+    k = min(n, DUMP_BYTES // 2 // world // (160 * 2 + 8))         # half the budget for the states of all ranks
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False)) if k < n else np.arange(n)
+    got = states[torch.from_numpy(idx).to(states.device)].cpu().numpy().view(np.uint64).reshape(k, 5, 4)
+    sfx = "" if world == 1 else "_rank%d" % rank
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "states%s.npy" % sfx), u64_halves(got))
+    np.save(os.path.join(out_dir, "state_index%s.npy" % sfx), (idx + first_perm).astype(np.float64))
+
+
+def hex_words(h: str):
+    """A 256-bit value as the line prints it (hex, high limb first) -> its four 64-bit limbs, low limb first."""
+    v = int(h, 16)
+    return [(v >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(4)]
+
+
+def dump_words(out_dir, name: str, words):
+    """--dump-outputs: a short list of 64-bit words (digest, root) as DIR/<name>.npy, halves as in u64_halves."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), u64_halves(np.array([w & 0xFFFFFFFFFFFFFFFF for w in words],
+                                                                      dtype=np.uint64)))
 
 
 class ShardCheck:
@@ -743,7 +788,11 @@ def main():
     ap.add_argument("--config5-full-size", action="store_true",
                     help="with --single-device at world size 8: run secondary.config5_2p30 at its real size (2^27 states per "
                          "rank, 160 GiB on the one device) instead of the rehearsal size (testing)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(launch_ranks(args))
@@ -830,6 +879,10 @@ def main():
     blocks_covered = sharding.reduce_sum_int(1 if block_ok is not None else 0, device)
     blocks_ok = sharding.reduce_sum_int(1 if block_ok else 0, device)
     digest = sharding.combine_digests(H.digest(states, first_index=20 * first_perm), device)
+    if args.dump_outputs:
+        dump_states(args.dump_outputs, states, first_perm, rank, world)
+        if rank == 0:
+            dump_words(args.dump_outputs, "digest", digest)
 
     del states, check
     torch.cuda.empty_cache()
@@ -981,6 +1034,8 @@ def bench_merkle(args, H, torch, device, sharding, rank, world):
     if rank != 0:
         return
     nodes = rec["nodes"]
+    if args.dump_outputs:
+        dump_words(args.dump_outputs, "root", hex_words(rec["root"]))
     out = {"metric": "Poseidon Merkle tree nodes/sec (arity 4, 2^24 leaves; Hades252 WIDTH=5)",
            "value": nodes * world / (ms * 1e-3), "unit": "nodes/s", "n_gpus": world, "steps": args.steps,
            "warmup": 1, "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,

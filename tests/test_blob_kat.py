@@ -6,9 +6,10 @@ The only reference-held artefacts that carry field-arithmetic results are the tw
 computed with that crate's `+`, `from_bytes_wide`, `From<u64>` and `invert`).  Here every one of
 those 985 x 32 bytes is regenerated THROUGH `oracle/hades_oracle.c`'s exported field operations
 (`fr_add`, `fr_mul`, `fr_square`, `fr_from_raw`) -- not through Python big integers -- and must
-equal the blob: sha256 always (hashes recorded in SURVEY.md section 4), byte for byte when
-/root/reference is present.  A wrong carry, reduction or conditional subtraction in the oracle's
-Montgomery arithmetic cannot survive ~19 000 chained operations that end on these bytes.
+equal the blob: sha256 (hashes recorded in SURVEY.md section 4) and byte for byte against the
+reference's files, stored as tests/golden/ark.bin / mds.bin.  A wrong carry, reduction or conditional
+subtraction in the oracle's Montgomery arithmetic cannot survive ~19 000 chained operations that end
+on these bytes.
 
   ark.bin  c_0 = from_bytes_wide(SHA512("poseidon-for-plonk")) + 1, c_i = from_bytes_wide(SHA512(prev digest)) + c_{i-1}
            from_bytes_wide(lo || hi) = lo * R^2 + hi * R^3  (Montgomery products; the published
@@ -26,7 +27,7 @@ from oracle_lib import P, R, limbs_of
 
 ARK_SHA256 = "78c427449282315729eaa2e39e1937e0aa0b010c4c38bcbb1d57016011880485"
 MDS_SHA256 = "131915cbeae1bde75422cce7fcf7feb9223a4dec370a937a2133c1f998ded0e7"
-REF_ASSETS = "/root/reference/assets"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")   # the reference's assets/ark.bin, mds.bin
 
 
 def le32(v):
@@ -73,9 +74,7 @@ def test_ark_blob_through_c_oracle_field_ops(oracle):
     blob = b"".join(le32(v) for v in limbs)
     assert len(blob) == 30720
     assert hashlib.sha256(blob).hexdigest() == ARK_SHA256
-    path = os.path.join(REF_ASSETS, "ark.bin")
-    if os.path.exists(path):
-        assert blob == open(path, "rb").read()
+    assert blob == open(os.path.join(GOLDEN, "ark.bin"), "rb").read()
     # the loader, through the oracle: chunk -> from_raw -> ROUND_CONSTANTS[i]
     for i in (0, 1, 4, 5, 334, 335, 959):
         assert oracle.fr1("from_raw", limbs[i]) == oracle.round_constant(i)
@@ -86,9 +85,7 @@ def test_mds_blob_through_c_oracle_field_ops(oracle):
     blob = b"".join(le32(v) for v in limbs)
     assert len(blob) == 800
     assert hashlib.sha256(blob).hexdigest() == MDS_SHA256
-    path = os.path.join(REF_ASSETS, "mds.bin")
-    if os.path.exists(path):
-        assert blob == open(path, "rb").read()
+    assert blob == open(os.path.join(GOLDEN, "mds.bin"), "rb").read()
     for i in range(5):
         for j in range(5):
             assert oracle.fr1("from_raw", limbs[5 * i + j]) == oracle.mds(i, j)
@@ -105,7 +102,7 @@ def test_mds_blob_through_c_oracle_field_ops(oracle):
 # ---------------------------------------------------------------------------------------------
 def blob_bytes(name):
     """The blob, regenerated with plain integers from the documented algorithm (HOWTO.md:21-39, :71-97),
-    sha256-pinned; the reference's file itself when /root/reference is present (this container)."""
+    sha256-pinned and equal to the reference's file itself (tests/golden/<name>.bin)."""
     import hashlib as h
     if name == "ark":
         run, data, out = 1, b"poseidon-for-plonk", []
@@ -119,9 +116,7 @@ def blob_bytes(name):
         want = MDS_SHA256
     blob = b"".join(v.to_bytes(32, "little") for v in out)
     assert h.sha256(blob).hexdigest() == want
-    path = os.path.join(REF_ASSETS, name + ".bin")
-    if os.path.exists(path):
-        assert blob == open(path, "rb").read()
+    assert blob == open(os.path.join(GOLDEN, name + ".bin"), "rb").read()
     return blob
 
 

@@ -1,6 +1,6 @@
 """GPU tier, SURVEY section 8 row e: the multi-GPU decompositions on the one device a test box has -- Merkle trees sharded by
 sub-tree (emulated ranks, virtual workers, against the oracle's committed roots) and the N > 1 path of bench.py rehearsed
-with two ranks on one device."""
+with two, three and four ranks on one device."""
 import ctypes
 import hashlib
 import json
@@ -104,41 +104,51 @@ def test_bench_two_ranks_rehearsal_prints_both_multi_rank_records(torch_cuda, ha
         json.dump(out, f)
 
 
-def test_bench_eight_ranks_rehearsal_is_the_production_split(torch_cuda, hades_lib, kat):
-    """World size 8 -- the node BASELINE configs[4] names -- with all eight ranks on the one device of the test box, at
-    rehearsal size: the tree splits into 16 sub-trees of 2^20 leaves, two per rank, the all_gather
-    carries 16 sub-roots, every rank's device is reported, and both multi-rank records come out TRUE."""
-    out, _ = _bench(["--gpus", "8", "--single-device", "--dist-backend", "gloo", "--perms-per-gpu", "262144", "--steps", "2",
-                     "--warmup", "1", "--cpu-sample", "4096"])
-    assert out["n_gpus"] == 8 and out["dist"]["ranks_seen"] == 8 and len(out["per_gpu"]["device"]) == 8
-    assert out["parity_vs_cpu_sample"] is True and len(out["per_gpu"]["kernel_ms_per_rank"]) == 8
+# Ranks that share the one device in the rehearsals below.  Every rank is a process with the GPU open, and so is this test
+# process: 4 ranks make 5.  A shared GPU test machine caps that number (at 6 where this suite is checked: eight ranks, nine
+# processes, were stopped there), so world size 8 keeps its split arithmetic on the CPU (tests/test_host_logic.py,
+# tests/test_sharding_gloo.py: 16 sub-trees, the committed sub-roots) and in-process above (8 and 16 virtual workers), and
+# bench.py's multi-rank path is rehearsed at the largest world that fits.
+ONE_DEVICE_RANKS = 4
+
+
+def test_bench_four_ranks_on_one_device_rehearse_the_multi_rank_path(torch_cuda, hades_lib, kat):
+    """World size 4, all ranks on the one device of the test box, at rehearsal size: the tree splits into 4 sub-trees of
+    2^22 leaves, one per rank, the all_gather carries 4 sub-roots, every rank's device is reported,
+    and both multi-rank records come out TRUE."""
+    w = ONE_DEVICE_RANKS
+    out, _ = _bench(["--gpus", str(w), "--single-device", "--dist-backend", "gloo", "--perms-per-gpu", "262144", "--steps",
+                     "2", "--warmup", "1", "--cpu-sample", "4096"])
+    assert out["n_gpus"] == w and out["dist"]["ranks_seen"] == w and len(out["per_gpu"]["device"]) == w
+    assert out["dist"]["single_device"] is True and len(set(out["per_gpu"]["device"])) == 1
+    assert out["parity_vs_cpu_sample"] is True and len(out["per_gpu"]["kernel_ms_per_rank"]) == w
     c5 = out["secondary"]["config5_rehearsal"]
-    assert c5["total_perms"] == 8 * 262144 and c5["parity_vs_cpu_sample"] is True and c5["digest_matches_one_device"] is True
+    assert c5["total_perms"] == w * 262144 and c5["parity_vs_cpu_sample"] is True and c5["digest_matches_one_device"] is True
     ms = out["secondary"]["merkle_2p24_sharded"]
-    assert ms["root_matches_golden"] is True and "2 sub-tree(s) of 1048576 leaves per rank" in ms["workload"]
-    assert "16 sub-roots" in ms["workload"] and "512 bytes" in ms["exchange"]
-    with open(os.path.join(ROOT, "gpurun_out", "bench_rehearsal_8ranks.json"), "w") as f:
-        json.dump(out, f)
+    assert ms["root_matches_golden"] is True and "1 sub-tree(s) of 4194304 leaves per rank" in ms["workload"]
+    assert "4 sub-roots" in ms["workload"] and "128 bytes" in ms["exchange"]
+    _record("bench_rehearsal_4ranks_one_device.jsonl", json.dumps(out))
 
 
-def test_bench_config5_full_size_through_the_eight_rank_path(torch_cuda, hades_lib, kat):
-    """BASELINE configs[4] through bench.py's own N = 8 code path at its REAL size -- 2^27 states per rank, all eight ranks on
-    the one device of the test box (160 GiB resident) -- the sum of the ranks' shard digests against the CPU oracle's digest of
-    all 2^30 outputs.  What an 8-GPU node will run, minus the seven other GPUs."""
+def test_bench_config5_full_size_through_the_four_rank_path(torch_cuda, hades_lib, kat):
+    """BASELINE configs[4] through bench.py's own multi-rank code path at its REAL size -- 2^28 states per rank, all four
+    ranks on the one device of the test box (160 GiB resident) -- every rank's shard digest against the CPU oracle's shard
+    digests it covers, and their sum against the oracle's digest of all 2^30 outputs."""
     import gc
     gc.collect()
     torch_cuda.cuda.empty_cache()                      # what earlier tests of this process left in torch's caching allocator
     free, _ = torch_cuda.cuda.mem_get_info()
     if free < (200 << 30):
         pytest.skip("needs 200 GiB of free HBM (%d GiB free)" % (free >> 30))
-    out, _ = _bench(["--gpus", "8", "--single-device", "--config5-full-size", "--dist-backend", "gloo", "--perms-per-gpu", "65536",
-                     "--steps", "1", "--warmup", "0", "--no-cpu-baseline"])
+    w = ONE_DEVICE_RANKS
+    out, _ = _bench(["--gpus", str(w), "--single-device", "--config5-full-size", "--dist-backend", "gloo", "--perms-per-gpu",
+                     "65536", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"])
     c5 = out["secondary"]["config5_2p30"]
-    assert c5["total_perms"] == 1 << 30 and c5["perms_per_gpu"] == 1 << 27 and len(c5["kernel_ms_per_rank"]) == 8
+    assert c5["total_perms"] == 1 << 30 and c5["perms_per_gpu"] == (1 << 30) // w and len(c5["kernel_ms_per_rank"]) == w
     assert c5["digest"] == kat["config5_2p30"]["oracle_digest"]
     assert c5["digest_matches_oracle_at_full_size"] is True and c5["parity_vs_cpu_sample"] is True
-    with open(os.path.join(ROOT, "gpurun_out", "bench_config5_full_size_8ranks_one_device.json"), "w") as f:
-        json.dump(out, f)
+    assert c5["shard_digests_match_oracle"] is True and c5["shards_covered"] == "%d of %d ranks" % (w, w)
+    _record("bench_config5_full_size_4ranks_one_device.jsonl", json.dumps(out))
 
 
 def test_bench_every_output_of_every_rank_against_the_oracle_at_headline_size(torch_cuda, hades_lib, kat):
