@@ -80,34 +80,40 @@ def device_source_hash() -> str:
     return h.hexdigest()
 
 
-def _fresh(want: str) -> bool:
-    if not (os.path.exists(LIB) and os.path.exists(STAMP)):
+def _fresh(lib: str, want: str) -> bool:
+    stamp = lib + ".stamp"
+    if not (os.path.exists(lib) and os.path.exists(stamp)):
         return False
-    with open(STAMP) as f:
+    with open(stamp) as f:
         return f.read().strip() == want
 
 
-def build(force: bool = False, verbose: bool = True) -> str:
-    want = source_hash()
-    if not force and _fresh(want):
-        return LIB
-    with open(LOCK, "w") as lock:
+def compile_so(lib: str, sources, want: str, cwd: str, force: bool = False, verbose: bool = True) -> str:
+    """hipcc FLAGS + sources -> lib (run in cwd), unless lib.stamp already holds `want`.  Serialised with lib.lock;
+    the library and then its stamp are replaced atomically, so concurrent callers never load a half-written file."""
+    if not force and _fresh(lib, want):
+        return lib
+    with open(lib + ".lock", "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:
-            if not force and _fresh(want):          # another process built it while we waited
-                return LIB
-            tmp = LIB + ".tmp.%d" % os.getpid()
-            cmd = [HIPCC] + FLAGS + ["-o", tmp] + SOURCES
+            if not force and _fresh(lib, want):     # another process built it while we waited
+                return lib
+            tmp = lib + ".tmp.%d" % os.getpid()
+            cmd = [HIPCC] + FLAGS + ["-o", tmp] + list(sources)
             if verbose:
                 print("[hades252_amd.build]", " ".join(cmd), flush=True)
-            subprocess.run(cmd, cwd=CSRC, check=True)
-            os.replace(tmp, LIB)
-            with open(STAMP + ".tmp", "w") as f:
+            subprocess.run(cmd, cwd=cwd, check=True)
+            os.replace(tmp, lib)
+            with open(lib + ".stamp.tmp", "w") as f:
                 f.write(want + "\n")
-            os.replace(STAMP + ".tmp", STAMP)
+            os.replace(lib + ".stamp.tmp", lib + ".stamp")
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
-    return LIB
+    return lib
+
+
+def build(force: bool = False, verbose: bool = True) -> str:
+    return compile_so(LIB, SOURCES, source_hash(), CSRC, force=force, verbose=verbose)
 
 
 # ---- native measurement tool of the host-pointer boundary (tools/host_path_bench.cpp) -------------------------

@@ -12,7 +12,8 @@ from oracle_lib import limbs_of, int_of  # noqa: E402
 from test_blob_kat import ARK_SHA256, MDS_SHA256, blob_bytes  # noqa: E402,F401
 
 __all__ = ["KERNELS", "TAG", "TAG4", "CAP", "SITES_PERM", "to_dev", "to_host", "hex_of", "scalars_dev", "rows",
-           "kernel_available", "each_state_is_input_or_output", "_record", "ARK_SHA256", "MDS_SHA256", "blob_bytes"]
+           "kernel_available", "each_state_is_input_or_output", "_record", "word_boundary_values", "ARK_SHA256", "MDS_SHA256",
+           "blob_bytes"]
 
 KERNELS = [1, 2, 3, 4, 5]   # HADES252_KERNEL_LITERAL, _FAST (one state per lane), _COOP (five waves per state), _LANES (one
                             # state per wave, elements spread over 16-lane rows), _ROWS (one state per row, four per wave)
@@ -60,3 +61,23 @@ def _record(name, text):
     os.makedirs(out, exist_ok=True)
     with open(os.path.join(out, name), "a") as f:
         f.write(text + "\n")
+
+
+def word_boundary_values():
+    """The per-32-bit-word boundary around p: (value, canonical?) pairs, for each word k: p + 2^(32 k) (not canonical),
+    p - 2^(32 k) (canonical), p's words above k with word k one lower and every word below it all ones (canonical), and p
+    with one word below k one higher (not canonical); then 2^255, 2^256 - 1, p (not canonical), p - 1 and 0."""
+    p = S.P
+    words = [(p >> (32 * k)) & 0xFFFFFFFF for k in range(8)]
+    out = []
+    for k in range(8):
+        out.append((p + (1 << (32 * k)), False))
+        out.append((p - (1 << (32 * k)), True))
+        if words[k] > 0:
+            out.append((p >> (32 * (k + 1)) << (32 * (k + 1)) | (words[k] - 1) << (32 * k) | ((1 << (32 * k)) - 1), True))
+        for j in range(k):
+            if words[j] < 0xFFFFFFFF:
+                out.append((p + (1 << (32 * j)), False))
+    out += [(1 << 255, False), ((1 << 256) - 1, False), (p, False), (p - 1, True), (0, True)]
+    assert all((v < p) == ok for v, ok in out)
+    return out

@@ -227,17 +227,30 @@ def test_wire_format_models():
     assert -P < val(mont_lin(D.to_limbs29(big), f_from)) < P
 
 
+# Adversarial operands of the bounds tests below, kept at module level: tests/test_gpu_a13_units.py drives the device
+# routines with the same inputs, so the model and the device are checked on the same extremes.
+# mont_lin: the largest normalised operands (every limb 2^29 - 1, top limb +-(2^25 - 1)) ...
+MONT_LIN_OPERANDS = [[MASK] * (NL - 1) + [top] for top in ((1 << 25) - 1, -((1 << 25) - 1), 0)]
+# ... and the word beside which a mont_lin1 result meets the linear layer
+MONT_LIN1_NEIGHBOUR = [MASK] * (NL - 1) + [(1 << 24) - 1]
+
+
+def mont_lin_factors():
+    """The constant factors the kernels hand mont_lin / mont_lin1: p - 1, the from_bytes map Rp R, FINAL_F, a K_r, one."""
+    sch = D.fast_schedule()
+    return [P - 1, D.RP * D.R % P, sch["final_f"], sch["part"][30][1], 1]
+
+
 def test_mont_lin_bounds_adversarial():
     """mont_lin on the largest normalised operands (every limb 2^29 - 1, top limb +-(2^25 - 1)): the model asserts the
     64-bit column bound, the digit-step exactness and the result range; reachable inputs are smaller."""
-    for top in ((1 << 25) - 1, -((1 << 25) - 1), 0):
-        a = [MASK] * (NL - 1) + [top]
-        for factor in (P - 1, D.RP * D.R % P, D.fast_schedule()["final_f"], D.fast_schedule()["part"][30][1], 1):
+    for a in MONT_LIN_OPERANDS:
+        for factor in mont_lin_factors():
             for steps in (2, 1):
                 r = mont_lin(a, factor, steps)
                 assert all(0 <= x < (1 << LB) for x in r[:-1])
                 if steps == 1:                                  # ... and the linear layer takes it as word 4 beside maximal words
-                    big = [MASK] * (NL - 1) + [(1 << 24) - 1]
+                    big = MONT_LIN1_NEIGHBOUR
                     for row in small_mds([big, big, big, big, r]):
                         assert normalised(row)
 
@@ -496,21 +509,30 @@ def test_trace_model_matches_spec_oracle():
         assert tr[66] == [S.to_mont(v) for v in out]
 
 
+# finalize32: the window's edges and the extremes of what the witness kernel hands it ...
+FINALIZE32_EDGES = [0, 1, -1, 31, -31, 32, (P >> 3) - 1, (P >> 3) - 2, -2 * P - (1 << 232) + 1, -2 * P, -P, -P + 1, -P - 1,
+                    P >> 4, -2 * P - (1 << 246)]
+# ... and the window's far edge (top limb about -2^28: beyond the schedule's own values, inside the kernel's 32-bit limbs)
+FINALIZE32_FAR = [-30 * P + 1, -29 * P - 17, -17 * P + 5]
+
+
+def far_limbs(v):
+    """Normalised limbs 0..7 and a signed top limb of v (the form FINALIZE32_FAR is driven in)."""
+    return D.to_limbs29(v % (1 << (LB * (NL - 1))))[:NL - 1] + [v >> (LB * (NL - 1))]
+
+
 def test_finalize32_window_adversarial():
     """finalize32 on the extremes of what the witness kernel hands it: products (mont_fips of lazy operands: (-p - 2^253,
     2^253)), rows with and without an appended constant ((-2p - eps, eps)), and the window's own edges."""
     rng = random.Random(59)
-    top = (P >> 3) - 1
-    for v in [0, 1, -1, 31, -31, 32, top, top - 1, -2 * P - (1 << 232) + 1, -2 * P, -P, -P + 1, -P - 1, P >> 4,
-              -2 * P - (1 << 246)] + \
+    for v in FINALIZE32_EDGES + \
              [rng.randrange(-2 * P, P >> 3) for _ in range(300)]:
         got = finalize32_model(D.to_balanced29_signed(v))
         assert got == v * pow(32, -1, P) % P
         if 0 <= v < (P >> 3):
             assert finalize32_model(D.to_limbs29(v)) == got                 # plain limbs, same value
-    # the window's far edge (top limb about -2^28: beyond the schedule's own values, inside the kernel's 32-bit limbs)
-    for v in (-30 * P + 1, -29 * P - 17, -17 * P + 5):
-        x = D.to_limbs29(v % (1 << (LB * (NL - 1)))) [:NL - 1] + [v >> (LB * (NL - 1))]
+    for v in FINALIZE32_FAR:
+        x = far_limbs(v)
         assert val(x) == v and finalize32_model(x) == v * pow(32, -1, P) % P
     # lazy limbs at the bound: a normalised value + a balanced addend
     for _ in range(50):
@@ -519,15 +541,18 @@ def test_finalize32_window_adversarial():
         assert finalize32_model(x) == (a + b - P) * pow(32, -1, P) % P
 
 
-def test_finalize32_after_rows_at_the_schedule_extremes():
-    """The row path at its worst: all five words U at the bottom of mont_lin's output range (about -p - 2^227, with and
-    without a lazy addend of about -p: the round constant seen through the map), the one-limb digit m steered to 2^29 - 1
-    (so that m p / 2^29 ~ p is subtracted), then the appended round constant at -p + 1 -- finalize32 receives about
-    -2 p - 2^245, below the window the comment used to state and inside the one that is asserted."""
-    rng = random.Random(67)
+# the round constants appended to a row before finalize32 in the test below: (-p, 0]
+ROW_CONSTANTS = (-P + 1, -(P >> 1), 0)
+
+
+def steered_rows(seed=67, trials=60):
+    """The row path's worst operands (test_finalize32_after_rows_at_the_schedule_extremes): yields (j, vals, u) -- output
+    row j, the five word values U and their lazy limbs -- with every word at the bottom of mont_lin's output range (about
+    -p - 2^227; every second trial with a lazy addend of about -p on top) and, for j < 4, the one-limb digit steered to
+    2^29 - 1 .. 2^29 - 4 through word 3 - j."""
+    rng = random.Random(seed)
     lo = -P - (1 << 227) + 1
-    worst = 0
-    for trial in range(60):
+    for trial in range(trials):
         base = [lo + rng.randrange(1 << 20) for _ in range(5)]
         if trial % 2:                                                    # words 0..3 of a partial round carry an addend
             base = [v - P + 1 + rng.randrange(1 << 10) for v in base]
@@ -538,15 +563,24 @@ def test_finalize32_after_rows_at_the_schedule_extremes():
                 assert D.MDS_SMALL[j][k] % 2 == 1
                 y0 = sum(D.MDS_SMALL[j][c] * vals[c] for c in range(5))
                 vals[k] += ((MASK - rng.randrange(4) - y0) * pow(D.MDS_SMALL[j][k], -1, 1 << LB)) & MASK
-            u = [D.to_balanced29_signed(v) for v in vals]
-            row = mds_row_cols(u, j, 5)
-            y = sum(D.MDS_SMALL[j][c] * vals[c] for c in range(5))
-            assert j == 4 or (y & MASK) >= MASK - 3
-            assert val(row) == (y - (y & MASK) * P) >> LB and ((y - (y & MASK) * P) & MASK) == 0
-            for c in (-P + 1, -(P >> 1), 0):
-                x = add_lazy(row, D.to_balanced29_signed(c)) if c else row
-                worst = min(worst, val(x))
-                assert finalize32_model(x) == (val(row) + c) * pow(32, -1, P) % P
+            yield j, vals, [D.to_balanced29_signed(v) for v in vals]
+
+
+def test_finalize32_after_rows_at_the_schedule_extremes():
+    """The row path at its worst: all five words U at the bottom of mont_lin's output range (about -p - 2^227, with and
+    without a lazy addend of about -p: the round constant seen through the map), the one-limb digit m steered to 2^29 - 1
+    (so that m p / 2^29 ~ p is subtracted), then the appended round constant at -p + 1 -- finalize32 receives about
+    -2 p - 2^245, below the window the comment used to state and inside the one that is asserted."""
+    worst = 0
+    for j, vals, u in steered_rows():
+        row = mds_row_cols(u, j, 5)
+        y = sum(D.MDS_SMALL[j][c] * vals[c] for c in range(5))
+        assert j == 4 or (y & MASK) >= MASK - 3
+        assert val(row) == (y - (y & MASK) * P) >> LB and ((y - (y & MASK) * P) & MASK) == 0
+        for c in ROW_CONSTANTS:
+            x = add_lazy(row, D.to_balanced29_signed(c)) if c else row
+            worst = min(worst, val(x))
+            assert finalize32_model(x) == (val(row) + c) * pow(32, -1, P) % P
     assert worst < -2 * P - (1 << 232), "the test did not reach below the old, too tight bound"
     assert worst > -2 * P - (1 << 247)
 
@@ -574,12 +608,15 @@ def test_per_op_models_match_spec_oracle():
         assert [finalize_model(x, op["w"]) for x in small_mds(pst)] == [S.to_mont(v) for v in exp]
 
 
+# mont_fips operands with limbs at the lazy extremes (positive and mixed-sign)
+PRODUCT_PATTERNS = [[LAZY - 1] * (NL - 1) + [(1 << 24) - 1],
+                    [LAZY - 1, -(1 << 28)] * 4 + [-(1 << 24)],
+                    [-(1 << 28)] * (NL - 1) + [(1 << 24)]]
+
+
 def test_product_bounds_adversarial():
     """Operand limbs at the lazy extremes (positive and mixed-sign): no signed 64-bit overflow."""
-    hi_limb = LAZY - 1
-    for pattern in ([hi_limb] * (NL - 1) + [(1 << 24) - 1],
-                    [hi_limb, -(1 << 28)] * 4 + [-(1 << 24)],
-                    [-(1 << 28)] * (NL - 1) + [(1 << 24)]):
+    for pattern in PRODUCT_PATTERNS:
         assert abs(val(pattern)) < (1 << 257)
         for sq in (False, True):
             r = mont_fips(pattern, pattern, sq)
@@ -612,10 +649,14 @@ def test_raw_32bit_quotient_digit_is_not_free():
     assert lazy_sq + 8 * (1 << 31) * (1 << 28) > I63 > lazy_sq + 8 * MASK * max(abs(x) for x in P29)
 
 
+# small_mds states with every limb at a lazy extreme
+_MDS_BIG = [LAZY - 1] * (NL - 1) + [(1 << 24) - 1]
+_MDS_NEG = [-(1 << 28)] * (NL - 1) + [-(1 << 24)]
+LINEAR_LAYER_STATES = [[_MDS_BIG] * 5, [_MDS_NEG] * 5, [_MDS_BIG, _MDS_NEG, _MDS_BIG, _MDS_NEG, _MDS_BIG]]
+
+
 def test_linear_layer_bounds_adversarial():
-    big = [LAZY - 1] * (NL - 1) + [(1 << 24) - 1]
-    neg = [-(1 << 28)] * (NL - 1) + [-(1 << 24)]
-    for st in ([big] * 5, [neg] * 5, [big, neg, big, neg, big]):
+    for st in LINEAR_LAYER_STATES:
         out = small_mds(st)
         for i in range(5):
             y = sum(D.MDS_SMALL[i][j] * val(st[j]) for j in range(5))
@@ -838,14 +879,26 @@ def test_lanes_model_matches_spec_oracle():
         assert got == [S.to_mont(v) for v in S.perm(vals)]
 
 
+# lane-product operands (nine limbs; a row appends seven zero lanes): limbs at the lazy maximum 2^30 + 1 and beyond, all
+# ones, sparse and tiny
+LANE_TOP = (1 << 25) - 1                                  # value < 2^258 (the kernel's values stay below 2^257)
+LANE_PATTERNS = [[LANE_IN_MAX] * (NL - 1) + [LANE_TOP], [MASK] * (NL - 1) + [LANE_TOP], [0] * NL, [1] + [0] * (NL - 1),
+                 [0] * (NL - 1) + [LANE_TOP], [LANE_IN_MAX, 0] * 4 + [LANE_TOP], [(1 << LB) + 2] * (NL - 1) + [LANE_TOP],
+                 [(1 << 30) + 1] * (NL - 1) + [LANE_TOP]]
+LANE_MDS_BIG = [LANE_IN_MAX] * (NL - 1) + [(1 << 26) - 1] + [0] * 7     # the result bound of a product
+
+
+def lane_lin_factors():
+    sch = D.fast_schedule()
+    return [P - 1, 1, sch["part"][17][1], sch["part"][62][1]]
+
+
 def test_lanes_product_bounds_adversarial():
     """Operand limbs at the lazy maximum 2^30 + 1 (both operands: the square of an S-box input after its round key),
     all-ones, sparse and tiny operands: no u64 / u32 overflow, exact division, zero-or-2^261 low part."""
     rng = random.Random(47)
-    top = (1 << 25) - 1                                   # value < 2^258 (the kernel's values stay below 2^257)
-    pats = [[LANE_IN_MAX] * (NL - 1) + [top], [MASK] * (NL - 1) + [top], [0] * NL, [1] + [0] * (NL - 1),
-            [0] * (NL - 1) + [top], [LANE_IN_MAX, 0] * 4 + [top], [(1 << LB) + 2] * (NL - 1) + [top],
-            [(1 << 30) + 1] * (NL - 1) + [top]]
+    top = LANE_TOP
+    pats = list(LANE_PATTERNS)
     pats += [[rng.randrange(LANE_IN_MAX + 1) for _ in range(NL - 1)] + [rng.randrange(top)] for _ in range(40)]
     rows = [p + [0] * 7 for p in pats]
     for a in rows:
@@ -853,10 +906,10 @@ def test_lanes_product_bounds_adversarial():
             r = lane_mont_mul(a, b)
             assert lane_val(r) % P == lane_val(a) * lane_val(b) * pow(D.RP, -1, P) % P
     for a in rows:                                        # the linear map by the row on the same operands
-        for factor in (P - 1, 1, D.fast_schedule()["part"][17][1], D.fast_schedule()["part"][62][1]):
+        for factor in lane_lin_factors():
             lane_lin(a, factor)
     # linear layer at its maxima
-    big = [LANE_IN_MAX] * (NL - 1) + [(1 << 26) - 1] + [0] * 7             # the result bound of a product
+    big = LANE_MDS_BIG
     for i in range(5):
         lane_mds_row(D.MDS_SMALL[i], [big] * 5)
         lane_mds_row(D.MDS_SMALL[i], [rows[0]] * 5)          # even straight after a round key

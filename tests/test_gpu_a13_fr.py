@@ -81,7 +81,26 @@ def test_fr_ops_vs_oracle_edge_values(torch_cuda, H, oracle):
             0xFFFFFFFF00000000, (P - 1) // 2, (P + 1) // 2, (1 << 128) - 1]
     a = [rng.choice(edge) if rng.random() < 0.6 else rng.randrange(P) for _ in range(700)]
     b = [rng.choice(edge) if rng.random() < 0.6 else rng.randrange(P) for _ in range(700)]
+    # ADD pairs whose sum is exactly p - 1, p, p + 1 and 2p - 2 (both sides of the conditional subtraction, and its
+    # boundary), and 0 + 0
+    for s in (P - 1, P, P + 1):
+        for x in (1, 2, (1 << 32) - 1, s // 2, P - 1, P - (1 << 32)):
+            if 0 <= s - x < P:
+                a.append(x)
+                b.append(s - x)
+    a += [P - 1, 0]
+    b += [P - 1, 0]
+    add_sums = {s: sum(1 for x, y in zip(a, b) if x + y == s) for s in (P - 1, P, P + 1, 2 * P - 2, 0)}
+    assert all(add_sums.values()), add_sums
+    # MUL pairs whose product is 0, one (R in Montgomery form: a a^-1) and p - 1 (its negation)
+    for _ in range(4):
+        x = rng.randrange(1, P)
+        xm, xinv = x * R % P, pow(x, -1, P) * R % P
+        a += [xm, xm, P - xm, 0, xm]
+        b += [xinv, P - xinv, xinv, xm, 0]
     da, db = scalars_dev(torch, a), scalars_dev(torch, b)
+    mul_of = {"zero": 0, "one": R, "minus one": P - R}
+    assert all(sum(1 for x, y in zip(a, b) if x * y * pow(R, -1, P) % P == v) for v in mul_of.values())
     for impl in (0, 1):
         got = to_host(H.fr_op(H.FR_ADD, da, db, impl=impl)).reshape(-1, 4)
         assert [int_of(r) for r in got] == [(x + y) % P for x, y in zip(a, b)]

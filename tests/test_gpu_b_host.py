@@ -410,6 +410,32 @@ def test_big_pageable_batch_goes_through_staging_threads(torch_cuda, H, hades_li
     assert lib.hades252_perm_batch_bytes(b2.ctypes.data, k) == -3 and (b2 == keep).all()
 
 
+def test_perm_batch_bytes_rejects_one_non_canonical_scalar_on_any_slice(torch_cuda, hades_lib):
+    """hades252_perm_batch_bytes on a batch of >= 2^18 scalars, where all_canonical_mt splits the check over (up to 8)
+    threads: ONE non-canonical scalar at the first position, on both sides of a slice boundary and at the last position
+    makes the call return -3 (HADES252_ERR_NOT_CANONICAL) and leaves the buffer untouched."""
+    lib = hades_lib
+    n_perms = (1 << 18) // 5 + 3                                          # 262 155 scalars: the threaded check
+    n = 5 * n_perms
+    assert n >= 1 << 18
+    rng = np.random.default_rng(7)
+    buf = np.zeros((n, 4), dtype=np.uint64)
+    buf[:, :3] = rng.integers(0, 1 << 63, size=(n, 3), dtype=np.uint64)   # canonical: the top word stays below p's
+    buf[:, 3] = rng.integers(0, 1 << 62, size=n, dtype=np.uint64)
+    bad_values = [S.P, (1 << 256) - 1, S.P + (1 << 192)]
+    positions = [0, n - 1]
+    for nt in (2, 4, 8):                                                  # the slice boundaries of 2, 4 and 8 threads
+        for t in range(1, nt):
+            b = n * t // nt
+            positions += [b - 1, b]
+    for i, pos in enumerate(sorted(set(positions))):
+        b2 = buf.copy()
+        b2[pos] = limbs_of(bad_values[i % len(bad_values)])
+        keep = b2.copy()
+        assert lib.hades252_perm_batch_bytes(b2.ctypes.data_as(ctypes.c_void_p), n_perms) == -3, pos
+        assert (b2 == keep).all(), pos
+
+
 def test_host_callers_under_injected_faults(torch_cuda, H, hades_lib, oracle):
     """hades252_merkle_root / _sponge_hash / _sponge_hash_var: a failing call returns a code, leaves the root untouched,
     and the same call then succeeds."""

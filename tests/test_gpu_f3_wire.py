@@ -21,6 +21,15 @@ from gpu_common import *  # noqa: E402,F401,F403  (helpers shared by the GPU tie
 pytestmark = pytest.mark.gpu
 
 
+def _from_bytes_count(torch, hades_lib, src, dst, n):
+    """hades252_from_bytes_dev on device buffers; returns the device's count of non-canonical inputs."""
+    bad = torch.zeros(1, dtype=torch.int32, device="cuda")
+    assert hades_lib.hades252_from_bytes_dev(src.data_ptr(), dst.data_ptr(), n, bad.data_ptr(),
+                                             torch.cuda.current_stream().cuda_stream) == 0
+    torch.cuda.synchronize()
+    return int(bad.item())
+
+
 def test_bytes_wire_format(torch_cuda, hades_lib, H, oracle):
     torch = torch_cuda
     rng = random.Random(3)
@@ -29,10 +38,44 @@ def test_bytes_wire_format(torch_cuda, hades_lib, H, oracle):
     dev = to_dev(torch, raw)
     limbs = H.from_bytes(dev)
     got = to_host(limbs).reshape(-1, 4)
-    for k in (0, 1, 2, 3, 500, 999):
-        assert int_of(got[k]) == vals[k] * R % P
+    assert [int_of(r) for r in got] == [v * R % P for v in vals]              # every output, not a sample
     back = H.to_bytes(limbs)
     assert (to_host(back) == raw).all()
+    # the per-32-bit-word boundary around p (the canonical check compares word by word), 2^255 and 2^256 - 1, among
+    # canonical values: exactly the bad ones are counted and zeroed, every good one is converted
+    bnd = word_boundary_values()
+    mixed = [bnd[i // 2] if i % 2 == 0 else (vals[i], True) for i in range(2 * len(bnd))]
+    mixed += [(v, True) for v in vals[:300]]
+    mraw = np.frombuffer(b"".join(v.to_bytes(32, "little") for v, _ in mixed), dtype=np.uint64).copy()
+    src = to_dev(torch, mraw)
+    out = torch.full_like(src, -1)
+    assert _from_bytes_count(torch, hades_lib, src, out, len(mixed)) == sum(1 for _, ok in mixed if not ok)
+    got = to_host(out).reshape(-1, 4)
+    for (v, ok), r in zip(mixed, got):
+        assert int_of(r) == (v * R % P if ok else 0), (hex(v), ok)
+    # in place (d_bytes == d_limbs, as the host pipeline converts a chunk): the same outputs
+    assert _from_bytes_count(torch, hades_lib, src, src, len(mixed)) == sum(1 for _, ok in mixed if not ok)
+    assert (to_host(src) == to_host(out)).all()
+    # ragged n, guard words behind the output (from_bytes handles two scalars per thread, at i and i + stride)
+    for n in (1, 2, 255, 256, 257, 511, 513):
+        guard = 64
+        src = to_dev(torch, raw[:4 * n])
+        out = torch.full((4 * n + guard,), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64, device="cuda")
+        assert _from_bytes_count(torch, hades_lib, src, out, n) == 0
+        h = to_host(out)
+        assert (h[4 * n:] == 0x5A5A5A5A5A5A5A5A).all(), "from_bytes wrote behind its output (n = %d)" % n
+        assert [int_of(r) for r in h[:4 * n].reshape(-1, 4)] == [v * R % P for v in vals[:n]], n
+        back = torch.full((4 * n + guard,), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64, device="cuda")
+        assert hades_lib.hades252_to_bytes_dev(out.data_ptr(), back.data_ptr(), n,
+                                               torch.cuda.current_stream().cuda_stream) == 0
+        h = to_host(back)
+        assert (h[4 * n:] == 0x5A5A5A5A5A5A5A5A).all(), "to_bytes wrote behind its output (n = %d)" % n
+        assert (h[:4 * n] == raw[:4 * n]).all(), n
+    # to_bytes in place as well
+    inplace = limbs.clone()
+    assert hades_lib.hades252_to_bytes_dev(inplace.data_ptr(), inplace.data_ptr(), len(vals),
+                                           torch.cuda.current_stream().cuda_stream) == 0
+    assert (to_host(inplace) == raw).all()
     # host entry point: whole permutation on canonical bytes
     n = 200
     host = raw[:n * 20].copy()
