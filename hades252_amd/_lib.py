@@ -25,6 +25,7 @@ KERNEL_COOP = 3
 KERNEL_LANES = 4
 KERNEL_ROWS = 5
 MULTI_VIRTUAL = 1
+CIPHER_MAX_LEN = 1024
 
 # every symbol include/hades252.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -119,6 +120,13 @@ SIGNATURES = {
     "hades252_sponge_init_dev": (c_int, [c_void_p, c_size_t, POINTER(c_uint64), c_void_p]),
     "hades252_sponge_absorb_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "hades252_sponge_squeeze_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "hades252_cipher_encrypt_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, POINTER(c_uint64), c_void_p,
+                                            c_void_p]),
+    "hades252_cipher_decrypt_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, POINTER(c_uint64), c_void_p,
+                                            c_void_p, c_void_p, c_void_p]),
+    "hades252_cipher_encrypt": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, POINTER(c_uint64), c_void_p]),
+    "hades252_cipher_decrypt": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, POINTER(c_uint64), c_void_p,
+                                        c_void_p, POINTER(c_size_t)]),
     "hades252_gen_b_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_uint64, c_void_p]),
     "hades252_gen_a_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_void_p]),
     "hades252_digest_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_void_p, c_void_p]),

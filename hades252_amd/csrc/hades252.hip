@@ -31,6 +31,7 @@ using namespace hades;
 #include "kernels_perm.hpp"
 #include "kernels_merkle.hpp"
 #include "kernels_sponge.hpp"
+#include "kernels_cipher.hpp"
 #include "kernels_aux.hpp"
 
 
@@ -42,8 +43,10 @@ using namespace hades;
 #include "abi_perm.hpp"
 #include "abi_merkle.hpp"
 #include "abi_sponge.hpp"
+#include "abi_cipher.hpp"
 #include "abi_util.hpp"
 #include "host_pin.hpp"
 #include "host_pool.hpp"
 #include "host_pipe.hpp"
 #include "host_callers.hpp"
+#include "host_cipher.hpp"

@@ -161,6 +161,7 @@ struct HostCall {                 // releases what a one-shot host call holds, w
     }
 };
 
+// (also used by host_cipher.hpp, included right after this file, which #undefs it)
 #define TRY_CALL(call, expr)                           \
     do {                                               \
         hipError_t e_ = (expr);                        \
@@ -399,6 +400,5 @@ int hades252_sponge_hash_var(const uint64_t *scalars, size_t n_scalars, const ui
     if (n_bad != nullptr) *n_bad = (size_t)bad;
     return call.finish(HADES252_OK);
 }
-#undef TRY_CALL
 
 }  // extern "C"

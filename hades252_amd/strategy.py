@@ -718,6 +718,107 @@ class SpongeStates:
         return out
 
 
+# ---- batched Poseidon cipher (include/hades252.h, CONVENTION UNPINNED) -----------------------------------------------
+_FR_P = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
+# dusk-poseidon's domain word: BlsScalar::from_raw([0x1_0000_0000, 0, 0, 0]) = 2^32, in Montgomery form (R = 2^256)
+CIPHER_DOMAIN = (1 << 32) * (1 << 256) % _FR_P
+
+
+def _same_device(what: str, dev, *others) -> None:
+    for d in others:
+        if d != dev:
+            raise ValueError("%s: every tensor must be on %s (got one on %s)" % (what, dev, d))
+
+
+def _cipher_shapes(what: str, msg_len: int, keys_units: int, nonces_units: int) -> int:
+    if not 1 <= msg_len <= _lib.CIPHER_MAX_LEN:
+        raise ValueError("%s: msg_len must be in 1 .. %d (got %d)" % (what, _lib.CIPHER_MAX_LEN, msg_len))
+    if keys_units != 2 * nonces_units:
+        raise ValueError("%s: %d key scalars for %d nonces (two per message)" % (what, keys_units, nonces_units))
+    return nonces_units
+
+
+def cipher_encrypt(msgs_t, keys_t, nonces_t, msg_len: int, domain_mont: int = CIPHER_DOMAIN):
+    """Batched Poseidon cipher, encrypt (``hades252_cipher_encrypt_dev``): msgs_t holds n messages of msg_len scalars,
+    keys_t n x 2 scalars, nonces_t n scalars (CUDA tensors, Montgomery limbs).  Returns [n, msg_len + 1, 4] int64: the
+    cipher words, the tag last."""
+    import torch
+    kptr, n_keys, dev = _dev_buffer(keys_t, 32, "cipher_encrypt")
+    nptr, n_nonces, ndev = _dev_buffer(nonces_t, 32, "cipher_encrypt")
+    mptr, n_words, mdev = _dev_buffer(msgs_t, 32, "cipher_encrypt")
+    _same_device("cipher_encrypt", dev, ndev, mdev)
+    n = _cipher_shapes("cipher_encrypt", msg_len, n_keys, n_nonces)
+    if n_words != n * msg_len:
+        raise ValueError("cipher_encrypt: buffer is not %d messages of %d scalars" % (n, msg_len))
+    out = torch.empty((n, msg_len + 1, 4), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().hades252_cipher_encrypt_dev(mptr, kptr, nptr, n, msg_len, _tag_arr(domain_mont), out.data_ptr(),
+                                                     _stream_ptr(dev)), "cipher_encrypt")
+    return out
+
+
+def cipher_decrypt(ciphers_t, keys_t, nonces_t, msg_len: int, domain_mont: int = CIPHER_DOMAIN):
+    """Batched Poseidon cipher, decrypt (``hades252_cipher_decrypt_dev``): ciphers_t holds n x (msg_len + 1) scalars.
+    Returns (msgs [n, msg_len, 4] int64, ok [n] uint8, n_rejected); a rejected message (wrong tag, or a cipher word that
+    is not canonical) comes out as zeros.  n_rejected synchronises with the device."""
+    import torch
+    kptr, n_keys, dev = _dev_buffer(keys_t, 32, "cipher_decrypt")
+    nptr, n_nonces, ndev = _dev_buffer(nonces_t, 32, "cipher_decrypt")
+    cptr, n_words, cdev = _dev_buffer(ciphers_t, 32, "cipher_decrypt")
+    _same_device("cipher_decrypt", dev, ndev, cdev)
+    n = _cipher_shapes("cipher_decrypt", msg_len, n_keys, n_nonces)
+    if n_words != n * (msg_len + 1):
+        raise ValueError("cipher_decrypt: buffer is not %d ciphers of %d scalars" % (n, msg_len + 1))
+    out = torch.empty((n, msg_len, 4), dtype=torch.int64, device=dev)
+    ok = torch.empty(n, dtype=torch.uint8, device=dev)
+    rej = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().hades252_cipher_decrypt_dev(cptr, kptr, nptr, n, msg_len, _tag_arr(domain_mont), out.data_ptr(),
+                                                     ok.data_ptr(), rej.data_ptr(), _stream_ptr(dev)), "cipher_decrypt")
+    return out, ok, int(rej.item())
+
+
+def _host_scalars(a, what: str) -> int:
+    a = _host_u64(a, what)
+    if a.size % 4:
+        raise ValueError("%s: %d limbs is not a whole number of scalars" % (what, a.size))
+    return a.size // 4
+
+
+def _ptr(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def cipher_encrypt_host(msgs: np.ndarray, keys: np.ndarray, nonces: np.ndarray, msg_len: int,
+                        domain_mont: int = CIPHER_DOMAIN) -> np.ndarray:
+    """``hades252_cipher_encrypt`` on HOST arrays (C-contiguous uint64, Montgomery limbs): -> [n, msg_len + 1, 4] uint64."""
+    n_words = _host_scalars(msgs, "cipher_encrypt_host")
+    n = _cipher_shapes("cipher_encrypt_host", msg_len, _host_scalars(keys, "cipher_encrypt_host"),
+                       _host_scalars(nonces, "cipher_encrypt_host"))
+    if n_words != n * msg_len:
+        raise ValueError("cipher_encrypt_host: buffer is not %d messages of %d scalars" % (n, msg_len))
+    out = np.zeros((n, msg_len + 1, 4), dtype=np.uint64)
+    check(_lib.lib().hades252_cipher_encrypt(_ptr(msgs), _ptr(keys), _ptr(nonces), n, msg_len, _tag_arr(domain_mont),
+                                             _ptr(out)), "cipher_encrypt_host")
+    return out
+
+
+def cipher_decrypt_host(ciphers: np.ndarray, keys: np.ndarray, nonces: np.ndarray, msg_len: int,
+                        domain_mont: int = CIPHER_DOMAIN):
+    """``hades252_cipher_decrypt`` on HOST arrays: -> (msgs [n, msg_len, 4] uint64, ok [n] uint8, n_rejected)."""
+    n_words = _host_scalars(ciphers, "cipher_decrypt_host")
+    n = _cipher_shapes("cipher_decrypt_host", msg_len, _host_scalars(keys, "cipher_decrypt_host"),
+                       _host_scalars(nonces, "cipher_decrypt_host"))
+    if n_words != n * (msg_len + 1):
+        raise ValueError("cipher_decrypt_host: buffer is not %d ciphers of %d scalars" % (n, msg_len + 1))
+    out = np.zeros((n, msg_len, 4), dtype=np.uint64)
+    ok = np.zeros(n, dtype=np.uint8)
+    rej = ctypes.c_size_t(0)
+    check(_lib.lib().hades252_cipher_decrypt(_ptr(ciphers), _ptr(keys), _ptr(nonces), n, msg_len, _tag_arr(domain_mont),
+                                             _ptr(out), _ptr(ok), ctypes.byref(rej)), "cipher_decrypt_host")
+    return out, ok, int(rej.value)
+
+
 GEN_SEED = 0x4861646573323532
 
 

@@ -409,6 +409,40 @@ int hades252_sponge_squeeze_dev(const void *d_states, void *d_digests, size_t n_
  *   "sponge/pad10"   capacity = 2^64 (Montgomery form), pad_mode 1 (a single 1, then zeros), digest = word 1
  *   "merkle/arity4"  tag = 2^4 - 1 = 15 in word 0, children in words 1..4, digest = word 1 */
 
+/* ---- batched Poseidon cipher (caller shape of dusk-poseidon's PoseidonCipher, README.md:9) ---- CONVENTION UNPINNED
+ * Authenticated encryption of n_msgs independent messages of msg_len scalars each (Montgomery limbs, as everywhere).
+ * dusk-poseidon is not part of the reference tree: the construction is recalled from that crate (<= 0.33), the domain
+ * word is a parameter and parity is pinned only to this repo's model (tests/cipher_model.py).  Per message, with key
+ * (kx, ky) (the shared secret's affine coordinates), nonce n, M = msg_len and D = domain_mont:
+ *   state = [D, M, kx, ky, n]   (M as the field element M)
+ *   encrypt: for each block of 4 words: perm; words 1.. += the block's message words, which are also the cipher words;
+ *            then perm; c[M] = word 1 (the tag).  M + 1 cipher words per message.
+ *   decrypt: the same chain (message word = cipher word - state word, state word = cipher word); then perm;
+ *            ok = (c[M] == word 1) and every cipher word canonical (< p); a rejected message comes out as M zeros.
+ * The crate's instance is M = 2, D = 2^32 (Montgomery form); for M <= 4 the block count ceil(M / 4) is the crate's, for
+ * larger M this is the natural generalisation.  Encrypt inputs must be canonical (not checked, as for perm).
+ * Layouts (AoS, 32 B per scalar): messages n x M, keys n x 2, nonces n x 1, ciphers n x (M + 1), ok n bytes.
+ * Rules: n_msgs = 0 is a no-op success; a NULL array with n_msgs > 0, msg_len 0 or > HADES252_CIPHER_MAX_LEN, a
+ * scalar array that is not 16-byte aligned, d_rejected not 4-byte aligned or n_msgs > 2^30 is HADES252_ERR_INVALID_ARG,
+ * all checked before the device is touched.  d_rejected (device int, may be NULL) is INCREMENTED by the number of
+ * rejected messages.  Up to 1 024 messages run one per wave (latency: about 2 x 52 us at M = 2), more run one per lane.
+ * Callers holding the 96-byte serialised form (three canonical 32-byte scalars) convert it with hades252_from_bytes_dev. */
+#define HADES252_CIPHER_MAX_LEN 1024
+/* dusk-poseidon's domain word 2^32 in the memory format (Montgomery limbs, least significant first), as an initialiser:
+ * uint64_t dom[4] = HADES252_CIPHER_DOMAIN_MONT; */
+#define HADES252_CIPHER_DOMAIN_MONT {0x355094eacaaf6b13ull, 0xf6b10cb369a568efull, 0xe2c926a640cc3869ull, 0x736a6d3bed269aadull}
+int hades252_cipher_encrypt_dev(const void *d_msgs, const void *d_keys, const void *d_nonces, size_t n_msgs, size_t msg_len,
+                                const uint64_t domain_mont[4], void *d_ciphers, void *stream);
+int hades252_cipher_decrypt_dev(const void *d_ciphers, const void *d_keys, const void *d_nonces, size_t n_msgs,
+                                size_t msg_len, const uint64_t domain_mont[4], void *d_msgs, uint8_t *d_ok, int *d_rejected,
+                                void *stream);
+/* The same on host memory (any n_msgs: chunked through a pooled pipe, device memory bounded; ordinary or page-locked
+ * memory).  *n_rejected (may be NULL) receives the number of rejected messages. */
+int hades252_cipher_encrypt(const uint64_t *msgs, const uint64_t *keys, const uint64_t *nonces, size_t n_msgs, size_t msg_len,
+                            const uint64_t domain_mont[4], uint64_t *ciphers);
+int hades252_cipher_decrypt(const uint64_t *ciphers, const uint64_t *keys, const uint64_t *nonces, size_t n_msgs,
+                            size_t msg_len, const uint64_t domain_mont[4], uint64_t *msgs, uint8_t *ok, size_t *n_rejected);
+
 /* ---- synthetic inputs and digests (benchmark / verification plumbing) --------------------- */
 /* Generator B: scalar e (global element index first_elem + k) gets 4 splitmix64 limbs, top limb
  * masked to 62 bits (always < p); see DESIGN.md.  Stateless, so shards generate independently. */

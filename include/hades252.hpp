@@ -183,6 +183,30 @@ inline void sponge_hash(const BlsScalar *msgs, std::size_t n_msgs, std::size_t m
                                reinterpret_cast<std::uint64_t *>(digests)), "sponge_hash");
 }
 
+// The batched Poseidon cipher on host memory (dusk-poseidon's PoseidonCipher shape; CONVENTION UNPINNED, include/hades252.h).
+// msgs: n x msg_len, keys: n x 2, nonces: n, ciphers: n x (msg_len + 1) scalars.  The crate's domain word is 2^32:
+// CIPHER_DOMAIN.
+constexpr BlsScalar CIPHER_DOMAIN{HADES252_CIPHER_DOMAIN_MONT};
+inline void cipher_encrypt(const BlsScalar *msgs, const BlsScalar *keys, const BlsScalar *nonces, std::size_t n_msgs,
+                           std::size_t msg_len, const BlsScalar &domain, BlsScalar *ciphers) {
+    check(hades252_cipher_encrypt(reinterpret_cast<const std::uint64_t *>(msgs), reinterpret_cast<const std::uint64_t *>(keys),
+                                  reinterpret_cast<const std::uint64_t *>(nonces), n_msgs, msg_len, domain.limbs,
+                                  reinterpret_cast<std::uint64_t *>(ciphers)),
+          "cipher_encrypt");
+}
+
+// ok[i] = 1 if cipher i authenticated (its message words in msgs), 0 if not (its message words zero); returns the number
+// of rejected messages.
+inline std::size_t cipher_decrypt(const BlsScalar *ciphers, const BlsScalar *keys, const BlsScalar *nonces, std::size_t n_msgs,
+                                  std::size_t msg_len, const BlsScalar &domain, BlsScalar *msgs, std::uint8_t *ok) {
+    std::size_t rejected = 0;
+    check(hades252_cipher_decrypt(reinterpret_cast<const std::uint64_t *>(ciphers), reinterpret_cast<const std::uint64_t *>(keys),
+                                  reinterpret_cast<const std::uint64_t *>(nonces), n_msgs, msg_len, domain.limbs,
+                                  reinterpret_cast<std::uint64_t *>(msgs), ok, &rejected),
+          "cipher_decrypt");
+    return rejected;
+}
+
 // What the library caches (pipes: streams, chunk buffers, staging memory) and which kernel a batch size gets.
 inline void trim() { check(hades252_trim(), "trim"); }
 inline std::size_t pool_bytes() { return hades252_pool_bytes(); }
