@@ -71,6 +71,11 @@ SIGNATURES = {
     "hades252_witness_wires": (c_int, []),
     "hades252_warm_up": (c_int, [c_size_t]),
     "hades252_perm_witness_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "hades252_sponge_blocks": (c_size_t, [c_size_t, c_int]),
+    "hades252_sponge_witness_dev": (c_int, [c_void_p, c_size_t, c_size_t, POINTER(c_uint64), c_int, c_void_p, c_void_p,
+                                            c_void_p, c_void_p]),
+    "hades252_merkle_open_witness_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_int, POINTER(c_uint64), c_void_p, c_void_p,
+                                                 c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hades252_add_round_key_dev": (c_int, [c_void_p, c_size_t, c_int, c_void_p]),
     "hades252_add_round_key_at_dev": (c_int, [c_void_p, c_size_t, c_int, c_void_p]),
     "hades252_apply_full_round_at_dev": (c_int, [c_void_p, c_size_t, c_int, c_void_p]),

@@ -1,0 +1,74 @@
+// abi_witness.hpp -- C ABI, device-resident data: gadget witnesses of the sponge (f1) and of Merkle openings (f2), the
+// permutation chains of row f4.  Every argument rule is checked before the device is touched; include/hades252.h holds the
+// contracts.
+#pragma once
+
+extern "C" {
+
+// permutations per message of hades252_sponge_hash_dev: ceil((msg_len + pad) / 4), at least one
+size_t hades252_sponge_blocks(size_t msg_len, int pad_mode) {
+    if (pad_mode != 0 && pad_mode != 1) return 0;
+    const size_t b = msg_len / 4 + (msg_len % 4 + (size_t)pad_mode + 3) / 4;
+    return b == 0 ? 1 : b;
+}
+
+int hades252_sponge_witness_dev(const void *d_msgs, size_t n_msgs, size_t msg_len, const uint64_t capacity_mont[4],
+                                int pad_mode, void *d_inputs, void *d_wires, void *d_digests, void *stream) {
+    if (n_msgs == 0) return HADES252_OK;
+    if (capacity_mont == nullptr || (d_msgs == nullptr && msg_len > 0) || (pad_mode != 0 && pad_mode != 1) ||
+        n_msgs > kMaxLaunchRecords || misaligned(d_msgs) || misaligned(d_digests) || d_inputs == nullptr ||
+        d_wires == nullptr || misaligned(d_inputs) || misaligned(d_wires))
+        return HADES252_ERR_INVALID_ARG;
+    const size_t blocks = hades252_sponge_blocks(msg_len, pad_mode);
+    if (blocks > kMaxLaunchRecords / n_msgs) return HADES252_ERR_INVALID_ARG;     // S * n_msgs records, at most 2^30
+    if (pad_mode == 1)
+        hipLaunchKernelGGL(k_witness_sponge<1>, dim3(blocks_for(n_msgs)), dim3(kBlock), 0, (hipStream_t)stream,
+                           (const uint8_t *)d_msgs, n_msgs, msg_len, blocks, fr_from_u64(capacity_mont), (uint8_t *)d_inputs,
+                           (uint8_t *)d_wires);
+    else
+        hipLaunchKernelGGL(k_witness_sponge<0>, dim3(blocks_for(n_msgs)), dim3(kBlock), 0, (hipStream_t)stream,
+                           (const uint8_t *)d_msgs, n_msgs, msg_len, blocks, fr_from_u64(capacity_mont), (uint8_t *)d_inputs,
+                           (uint8_t *)d_wires);
+    HIP_TRY(hipGetLastError());
+    if (d_digests != nullptr) {     // word 1 of the final states: r2[1] of the last round, records (S - 1) n .. S n - 1
+        const size_t plane = blocks * n_msgs, first = (size_t)(kWitnessLastRow + 2) * plane + (blocks - 1) * n_msgs;
+        HIP_TRY(hipMemcpyAsync(d_digests, (const uint8_t *)d_wires + first * 32, n_msgs * 32, hipMemcpyDeviceToDevice,
+                               (hipStream_t)stream));
+    }
+    return HADES252_OK;
+}
+
+// The tree holds every node, so the depth x n_queries permutations of the openings are independent: one gather of their
+// input states, then ONE k_perm_witness launch over all of them.
+int hades252_merkle_open_witness_dev(const void *d_leaves, const void *d_tree, size_t n_leaves, int arity,
+                                     const uint64_t tag_mont[4], const void *d_pad, const uint64_t *d_indices,
+                                     size_t n_queries, void *d_inputs, void *d_wires, int *d_bad_count, void *stream) {
+    const int depth = hades252_merkle_depth(n_leaves, arity);
+    if (depth < 1) return HADES252_ERR_INVALID_ARG;
+    if (n_queries == 0) return HADES252_OK;
+    if (d_leaves == nullptr || d_tree == nullptr || d_indices == nullptr || tag_mont == nullptr || d_inputs == nullptr ||
+        d_wires == nullptr || misaligned(d_leaves) || misaligned(d_tree) || misaligned(d_pad) || misaligned(d_inputs) ||
+        misaligned(d_wires) || ((uintptr_t)d_bad_count & 3u) != 0)
+        return HADES252_ERR_INVALID_ARG;
+    if ((size_t)depth > kMaxLaunchRecords / n_queries) return HADES252_ERR_INVALID_ARG;
+    const size_t n_perms = (size_t)depth * n_queries;
+    hipStream_t s = (hipStream_t)stream;
+    const Fr tag = fr_from_u64(tag_mont);
+#define HADES_LAUNCH_PATH_STATES(A)                                                                                  \
+    hipLaunchKernelGGL(k_witness_path_states<A>, dim3(blocks_for(n_perms * 5)), dim3(kBlock), 0, s,                  \
+                       (const uint8_t *)d_leaves, (const uint8_t *)d_tree, n_leaves, depth, d_indices, n_queries, tag, \
+                       (const uint8_t *)d_pad, (uint8_t *)d_inputs, d_bad_count)
+    switch (arity) {
+        case 2: HADES_LAUNCH_PATH_STATES(2); break;
+        case 3: HADES_LAUNCH_PATH_STATES(3); break;
+        default: HADES_LAUNCH_PATH_STATES(4); break;
+    }
+#undef HADES_LAUNCH_PATH_STATES
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_perm_witness, dim3(blocks_for(n_perms)), dim3(kBlock), 0, s, (const uint8_t *)d_inputs,
+                       (uint8_t *)d_wires, n_perms);
+    HIP_TRY(hipGetLastError());
+    return HADES252_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,207 @@
+// kernels_witness.hpp -- gadget witnesses of permutation chains (extended): the sponge witness as one
+// fused kernel, the input states of Merkle openings as a gather in front of k_perm_witness
+// Part of the single translation unit hades252.hip (included there after kernels_perm.hpp); not a stand-alone header.
+#pragma once
+
+// A batch of n chains of S steps is S * n permutations, record rec = s * n + i (step-major, chain within the step): the
+// lanes of a wave write consecutive records of every wire plane, as k_perm_witness does.  The record's input state goes to
+// inputs[rec] (160 B, the AoS format of the perm entry points), its 972 gate outputs to the wire planes of length S * n --
+// exactly what hades252_perm_witness_dev writes for those inputs.
+//
+// The two pieces below restate k_perm_witness (kernels_perm.hpp) operation for operation: the map of an in-memory state to
+// the Rp form (witness_enter) and the round loop (witness_rounds).  Same helpers (store_wire, finalize32, mds_row_cols,
+// mont_lin_words), same tables (d_wit), same fences and rolled loops, hence the same limbs and the same register budget.
+// kernels_perm.hpp is left as it is because the committed counter records are keyed by its bytes; folding k_perm_witness
+// onto these two is a follow-up for the next counter measurement.
+constexpr int kWitnessLastRow = HADES_WITNESS_WIRES - 9;    // r2[0] of the last round; r2[j] is wire kWitnessLastRow + 2 j
+__device__ __forceinline__ void witness_enter(const Fr (&in)[5], F29 (&y)[5]) {
+#pragma unroll
+    for (int w = 0; w < 5; w++) y[w] = to_f29(in[w]);
+#pragma unroll 1
+    for (int i = 0; i < 5; i++) {                       // in-memory limbs (x 2^256) -> x Rp
+        int off = 0;                                    // opaque offset: the 81 multipliers stay inside the loop
+        asm volatile("" : "+s"(off));
+        y[4] = mont_lin(y[4], d_wit.in_lin + off);
+        rotate_right(y);
+#pragma unroll
+        for (int w = 0; w < 5; w++)
+#pragma unroll
+            for (int k = 0; k < kNL; k++) limb_fence(y[w].l[k]);
+    }
+}
+
+__device__ __forceinline__ void witness_rounds(F29 (&y)[5], uint8_t *__restrict__ wires, size_t plane, size_t rec, bool live) {
+    int wire = 0;
+#pragma unroll 1
+    for (int r = 0; r < 67; r++) {
+        const int32_t *c = d_wit.c[r], *ck = d_wit.ck[r];
+        const bool full = r < 4 || r >= 63;
+        if (r == 0) {
+#pragma unroll 1
+            for (int i = 0; i < 5; i++) {               // state after the first round key: word 4 - i sits at y[4]
+                F29 s = y[4];
+                add_lazy(s, c + (4 - i) * kNL);
+                store_wire(wires, plane, wire + 4 - i, rec, live, finalize32(s));
+                rotate_right(y);
+            }
+            wire += 5;
+        }
+        const int cnt = full ? 5 : 1;                   // S-boxes: every word (rotating through y[4]) or word 4 alone
+#pragma unroll 1
+        for (int i = 0; i < cnt; i++) {
+            const int w = 4 - i;
+            const int g = wire + (full ? 3 * w : 0);
+            F29 z = y[4];
+            add_lazy(z, c + w * kNL);
+#pragma unroll
+            for (int k = 0; k < kNL; k++) limb_fence(z.l[k]);
+            F29 v2 = mont_sqr(z);
+            store_wire(wires, plane, g, rec, live, finalize32(v2));
+#pragma unroll
+            for (int k = 0; k < kNL; k++) limb_fence(v2.l[k]);
+            F29 v4 = mont_sqr(v2);
+            store_wire(wires, plane, g + 1, rec, live, finalize32(v4));
+#pragma unroll
+            for (int k = 0; k < kNL; k++) {
+                limb_fence(v4.l[k]);
+                limb_fence(z.l[k]);
+            }
+            z = mont_mul(v4, z);
+            store_wire(wires, plane, g + 2, rec, live, finalize32(z));
+            y[4] = z;
+            if (full) rotate_right(y);
+#pragma unroll
+            for (int w2 = 0; w2 < 5; w2++)
+#pragma unroll
+                for (int k = 0; k < kNL; k++) limb_fence(y[w2].l[k]);
+        }
+        wire += 3 * cnt;
+        {                                               // U_w = Y_w lam 2^29 (+ the round constant of words 0..3, partial)
+            int off = 0;
+            asm volatile("" : "+s"(off));
+            mont_lin_words<3>(y, d_wit.k_lin + off);
+            int off2 = 0;
+            asm volatile("" : "+s"(off2));
+            mont_lin_words<2>(y + 3, d_wit.k_lin + off2);
+            if (!full) {
+#pragma unroll
+                for (int w = 0; w < 4; w++) add_lazy(y[w], ck + w * kNL);
+            }
+        }
+#pragma unroll 1
+        for (int j = 0; j < 5; j++) {                   // r1[j]: columns 0..2 of row j
+#pragma unroll
+            for (int w = 0; w < 3; w++)
+#pragma unroll
+                for (int k = 0; k < kNL; k++) limb_fence(y[w].l[k]);
+            store_wire(wires, plane, wire + 2 * j, rec, live, finalize32(mds_row_cols<3>(d_coop.mds[j], y)));
+        }
+        small_mds(y);
+        const int32_t *cn = d_wit.c[r + 1];             // r2[j] = row j + the next round's constant (c[67] = 0)
+#pragma unroll
+        for (int j = 0; j < 5; j++) {
+            F29 s = y[j];
+            add_lazy(s, cn + j * kNL);
+            store_wire(wires, plane, wire + 2 * j + 1, rec, live, finalize32(s));
+        }
+#pragma unroll
+        for (int w = 0; w < 5; w++)
+#pragma unroll
+            for (int k = 0; k < kNL; k++) limb_fence(y[w].l[k]);
+        wire += 10;
+    }
+}
+
+// Sponge witness: lane i runs message i (the semantics of hades252_sponge_hash_dev: state = [capacity, 0, 0, 0, 0], block
+// b of 4 scalars added to words 1..4, then a permutation; pad_mode 1 appends a single 1 first; at least one block) and
+// records permutation b at rec = b * n + i.  Between blocks the state lives where the gadget has it: the last round's r2
+// wires, in memory.  The lane reads its own five r2 records back (160 B against 31 104 B it has just written; its own
+// earlier stores, so no fence) and adds the next block with fr_add, as the sponge kernels do: the state held across the
+// chain costs no registers inside the round loop, which is why the budget is k_perm_witness's (three waves per SIMD, no
+// scratch).  One message costs `blocks` x the latency of one k_perm_witness lane.  The digests (word 1 of the final states)
+// are n consecutive records of one wire plane: the caller copies them out.
+template <int PAD>
+__global__ void __launch_bounds__(kBlock, 3) k_witness_sponge(const uint8_t *__restrict__ msgs, size_t n, size_t msg_len,
+                                                              size_t blocks, Fr capacity, uint8_t *__restrict__ inputs,
+                                                              uint8_t *__restrict__ wires) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool live = i < n;
+    const size_t plane = blocks * n;
+    // the state before block 0, [capacity, 0, 0, 0, 0], is parked in the lane's first input record (which block 0 then
+    // overwrites): read back like every later state, the capacity holds no registers inside the chain.  (SGPR budget: the
+    // chain carries as few uniform values as it can -- the step as the record offset `base`, the message as the words
+    // still to come `rem` and a lane pointer, the padding as a template parameter.)
+    if (live) {
+        store_word(inputs + i * 160, capacity);
+#pragma unroll
+        for (int w = 1; w < 5; w++) store_word(inputs + i * 160 + w * 32, zero_word());
+    }
+    const uint8_t *mine = msgs + (live ? i * msg_len * 32 : 0);
+    int64_t rem = (int64_t)msg_len;                     // message words from this block on (<= 4 * 2^30)
+#pragma unroll 1
+    for (size_t base = 0; base < plane; base += n) {    // base = b * n: step b
+        const size_t rec = base + i;
+        // the previous state: the parked one, or the previous permutation's output (r2 of its last round)
+        const uint8_t *src = base == 0 ? inputs + i * 160 : wires + ((size_t)kWitnessLastRow * plane + rec - n) * 32;
+        const size_t stride = base == 0 ? 32 : 2 * plane * 32;
+        Fr in[5];
+#pragma unroll
+        for (int w = 0; w < 5; w++) in[w] = live ? load_word(src + w * stride) : zero_word();
+#pragma unroll
+        for (int k = 0; k < 4; k++) {                   // absorb: the gadget's add gates, words 1..4
+            Fr v = live && k < rem ? load_word(mine + k * 32) : zero_word();
+            if (PAD == 1 && k == rem) v = one_mont_word();
+            in[1 + k] = fr_add(in[1 + k], v);
+        }
+        mine += 128;
+        rem -= 4;
+        if (live) {
+#pragma unroll
+            for (int w = 0; w < 5; w++) store_word(inputs + rec * 160 + w * 32, in[w]);
+        }
+        F29 y[5];
+        witness_enter(in, y);
+        witness_rounds(y, wires, plane, rec, live);
+    }
+}
+
+// Merkle opening inputs: record rec = l * n_queries + q is the permutation that makes the level-(l + 1) ancestor of leaf
+// indices[q]: [tag, the ARITY children of its group at level l (level 0 = the leaves, level l >= 1 = tree level l, the layout
+// of hades252_merkle_build_dev), 0 ...]; a child position past the end of level l reads pad[l] (NULL: zero).  An index
+// >= n_leaves reads nothing and gets all-zero states (counted once, at l = 0).  One thread per (record, word).
+template <int ARITY>
+__global__ void __launch_bounds__(kBlock) k_witness_path_states(const uint8_t *__restrict__ leaves,
+                                                                const uint8_t *__restrict__ tree, size_t n_leaves, int depth,
+                                                                const uint64_t *__restrict__ indices, size_t n_queries,
+                                                                Fr tag, const uint8_t *__restrict__ pad,
+                                                                uint8_t *__restrict__ inputs, int *bad_count) {
+    const size_t tid = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    const size_t n_recs = (size_t)depth * n_queries;
+    if (tid >= n_recs * 5) return;
+    const size_t rec = tid / 5;
+    const int w = (int)(tid - rec * 5);
+    const int l = (int)(rec / n_queries);
+    const size_t q = rec - (size_t)l * n_queries;
+    size_t node = indices[q];
+    Fr v = zero_word();
+    if (node >= n_leaves) {
+        if (l == 0 && w == 0 && bad_count != nullptr) atomicAdd(bad_count, 1);
+    } else if (w == 0) {
+        v = tag;
+    } else if (w <= ARITY) {
+        const uint8_t *level = leaves;
+        size_t level_n = n_leaves, off = 0;
+        for (int k = 0; k < l; k++) {
+            node /= ARITY;
+            level_n = (level_n + ARITY - 1) / ARITY;
+            level = tree + off;
+            off += level_n * 32;
+        }
+        const size_t child = node - node % ARITY + (size_t)(w - 1);
+        if (child < level_n)
+            v = load_word(level + child * 32);
+        else
+            v = load_pad(pad + (pad != nullptr ? (size_t)l * 32 : 0));
+    }
+    store_word(inputs + rec * 160 + (size_t)w * 32, v);
+}

@@ -421,6 +421,66 @@ def perm_witness(states_t, out=None):
     return wires
 
 
+
+def sponge_blocks(msg_len: int, pad_mode: int = 1) -> int:
+    """Permutations per message of the fixed-length sponge (``hades252_sponge_blocks``): ceil((msg_len + pad) / 4), at
+    least one."""
+    if pad_mode not in (0, 1):
+        raise ValueError("sponge_blocks: pad_mode must be 0 or 1")
+    return int(_lib.lib().hades252_sponge_blocks(msg_len, pad_mode))
+
+
+def sponge_witness(msgs_t, msg_len: int, capacity_mont: int, pad_mode: int = 1, digests: bool = False):
+    """Gadget witness of the fixed-length sponge (``hades252_sponge_witness_dev``): msgs_t holds n messages of msg_len
+    scalars (msg_len 0: a tensor of shape [n, 0, ...] names n).  Returns (wires [972, S, n, 4], inputs [S, n, 5, 4]
+    [, digests [n, 4]]) with S = sponge_blocks(msg_len, pad_mode): inputs[s, i] is the state that enters permutation s of
+    message i and wires.reshape(972, S * n, 4) == perm_witness(inputs) byte for byte."""
+    import torch
+    if msg_len < 0:
+        raise ValueError("sponge_witness: msg_len must not be negative")
+    if msg_len > 0:
+        ptr, n_scalars, dev = _dev_buffer(msgs_t, 32, "sponge_witness")
+        if n_scalars % msg_len != 0:
+            raise ValueError("sponge_witness: buffer is not a whole number of messages")
+        n = n_scalars // msg_len
+    else:
+        if not isinstance(msgs_t, torch.Tensor) or msgs_t.device.type != "cuda" or msgs_t.dim() < 1:
+            raise TypeError("sponge_witness: msg_len 0 needs a CUDA tensor of shape [n, 0, ...]")
+        ptr, n, dev = None, int(msgs_t.shape[0]), msgs_t.device
+    S = sponge_blocks(msg_len, pad_mode)
+    wires = torch.empty((witness_wires(), S, n, 4), dtype=torch.int64, device=dev)
+    inputs = torch.empty((S, n, 5, 4), dtype=torch.int64, device=dev)
+    dig = torch.empty((n, 4), dtype=torch.int64, device=dev) if digests else None
+    with torch.cuda.device(dev):
+        check(_lib.lib().hades252_sponge_witness_dev(ptr, n, msg_len, _tag_arr(capacity_mont), pad_mode, inputs.data_ptr(),
+                                                     wires.data_ptr(), None if dig is None else dig.data_ptr(),
+                                                     _stream_ptr(dev)), "sponge_witness")
+    return (wires, inputs, dig) if digests else (wires, inputs)
+
+
+def merkle_open_witness(leaves_t, tree_t, arity: int, indices_t, tag_mont: int, pad=None):
+    """Gadget witness of Merkle openings (``hades252_merkle_open_witness_dev``) over the tree of ``merkle_build`` (same
+    arity, tag, pad).  Returns (wires [972, depth, n_queries, 4], inputs [depth, n_queries, 5, 4], n_bad): inputs[l, q] =
+    [tag, the children of the level-l group on leaf indices[q]'s path, 0 ...]; an index >= n_leaves gets all-zero states
+    and is counted in n_bad (synchronises with the device)."""
+    import torch
+    ptr, n, dev = _dev_buffer(leaves_t, 32, "merkle_open_witness")
+    depth = merkle_depth(n, arity, "merkle_open_witness")
+    tptr, nt, _ = _dev_buffer(tree_t, 32, "merkle_open_witness")
+    if nt != sum(merkle_level_sizes(n, arity)):
+        raise ValueError("merkle_open_witness: tree buffer does not belong to %d leaves" % n)
+    iptr, nq, _ = _dev_buffer(indices_t, 8, "merkle_open_witness")
+    wires = torch.empty((witness_wires(), depth, nq, 4), dtype=torch.int64, device=dev)
+    inputs = torch.empty((depth, nq, 5, 4), dtype=torch.int64, device=dev)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().hades252_merkle_open_witness_dev(ptr, tptr, n, arity, _tag_arr(tag_mont),
+                                                          _pad_ptr(pad, depth, "merkle_open_witness"), iptr, nq,
+                                                          inputs.data_ptr(), wires.data_ptr(), bad.data_ptr(),
+                                                          _stream_ptr(dev)), "merkle_open_witness")
+    return wires, inputs, int(bad.item())
+
+
 FR_ADD, FR_MUL, FR_SQUARE, FR_FROM_RAW, FR_REDUCE_SIGNED = 0, 1, 2, 3, 4
 FR_IMPL_SATURATED32, FR_IMPL_RADIX29 = 0, 1
 

@@ -249,6 +249,39 @@ int hades252_perm_trace_scale_table(uint64_t *mul, uint64_t *add);
 int hades252_witness_wires(void);
 int hades252_perm_witness_dev(const void *d_states, void *d_wires, size_t n_perms, void *stream);
 
+/* ---- gadget witnesses of permutation chains: the sponge (f1) and Merkle openings (f2) ---- CONVENTION UNPINNED
+ * The conventions are those of f1 and f2 below (capacity, padding, tag: parameters, still unpinned).  A batch of n chains
+ * of S steps is S * n permutations, numbered rec = s * n + i (step-major, chain within the step):
+ *   d_inputs receives S * n states of 160 B (the AoS format of the perm entry points): state rec enters permutation (s, i);
+ *   d_wires  receives 972 * S * n scalars, wire-major, exactly as hades252_perm_witness_dev writes them.
+ * Defining property: wires == hades252_perm_witness_dev(inputs) byte for byte, the S * n states taken as one flat batch.
+ * The gadget's selection and add gates (which children, where the path node sits; the block added into words 1..4) are the
+ * consumer's: the inputs carry their values.  A prover slices [972, S, n] per circuit.
+ *
+ * Sponge: the semantics of hades252_sponge_hash_dev (padding, the empty message, argument rules), S =
+ * hades252_sponge_blocks(msg_len, pad_mode) (0 for an invalid pad_mode).  inputs[0][i] = [capacity, block 0];
+ * inputs[s][i] = the output of permutation (s - 1, i) with block s added to words 1..4 (the absorb add gates' outputs).
+ * d_digests (may be NULL) receives word 1 of the final state: hades252_sponge_hash_dev's digest.  One message per lane,
+ * the state carried across its blocks: one message costs S x the latency of one perm_witness lane (no latency form).
+ *
+ * Merkle opening: the tree of hades252_merkle_build[_pad]_dev with the same arity, tag and pad (d_pad may be NULL, as
+ * there), S = hades252_merkle_depth(n_leaves, arity).  inputs[l][q] = [tag, the arity children of the level-l group that
+ * holds the level-l ancestor of leaf d_indices[q], 0 ...]: level 0 is the leaves, level l >= 1 comes from d_tree, a child
+ * position past the end of its level reads pad[l] (zero without a table).  The permutations are independent: one gather
+ * launch, then one perm_witness launch over all S * n_queries states.  An index >= n_leaves reads nothing outside the tree,
+ * gets all-zero input states (and their wires) and increments *d_bad_count (device int, may be NULL).
+ *
+ * Rules (both): n = 0 is a no-op success (for the opening: after the tree shape is checked); d_inputs and d_wires must be
+ * non-NULL and 16-byte aligned; S * n must be at most 2^30; besides those of hades252_sponge_hash_dev or
+ * hades252_merkle_open_pad_dev (and a non-NULL tag, a 4-byte aligned d_bad_count).  All are checked before the device is
+ * touched. */
+size_t hades252_sponge_blocks(size_t msg_len, int pad_mode);
+int hades252_sponge_witness_dev(const void *d_msgs, size_t n_msgs, size_t msg_len, const uint64_t capacity_mont[4],
+                                int pad_mode, void *d_inputs, void *d_wires, void *d_digests, void *stream);
+int hades252_merkle_open_witness_dev(const void *d_leaves, const void *d_tree, size_t n_leaves, int arity,
+                                     const uint64_t tag_mont[4], const void *d_pad, const uint64_t *d_indices,
+                                     size_t n_queries, void *d_inputs, void *d_wires, int *d_bad_count, void *stream);
+
 /* ---- the trait's per-operation methods, batched on device ------------------------------- */
 /* Strategy::add_round_key (src/strategies/scalar.rs:23-30).  The trait method takes the constants
  * ITERATOR (src/strategies.rs:33-41, :50-52); `cursor` is its position: word w of every state +=

@@ -207,6 +207,24 @@ inline std::size_t cipher_decrypt(const BlsScalar *ciphers, const BlsScalar *key
     return rejected;
 }
 
+// Gadget witnesses of permutation chains, DEVICE memory (e.g. DeviceBuffer::ptr()), enqueued on `stream`
+// (include/hades252.h): permutation (s, i) is record s * n + i; d_inputs gets S * n states, d_wires 972 planes of S * n
+// scalars -- what hades252_perm_witness_dev writes for those states.
+inline std::size_t sponge_blocks(std::size_t msg_len, bool pad_one) { return hades252_sponge_blocks(msg_len, pad_one ? 1 : 0); }
+
+inline void sponge_witness(const void *d_msgs, std::size_t n_msgs, std::size_t msg_len, const BlsScalar &capacity, bool pad_one,
+                           void *d_inputs, void *d_wires, void *d_digests = nullptr, void *stream = nullptr) {
+    check(hades252_sponge_witness_dev(d_msgs, n_msgs, msg_len, capacity.limbs, pad_one ? 1 : 0, d_inputs, d_wires, d_digests,
+                                      stream), "sponge_witness");
+}
+
+inline void merkle_open_witness(const void *d_leaves, const void *d_tree, std::size_t n_leaves, int arity, const BlsScalar &tag,
+                                const void *d_pad, const std::uint64_t *d_indices, std::size_t n_queries, void *d_inputs,
+                                void *d_wires, int *d_bad_count = nullptr, void *stream = nullptr) {
+    check(hades252_merkle_open_witness_dev(d_leaves, d_tree, n_leaves, arity, tag.limbs, d_pad, d_indices, n_queries, d_inputs,
+                                           d_wires, d_bad_count, stream), "merkle_open_witness");
+}
+
 // What the library caches (pipes: streams, chunk buffers, staging memory) and which kernel a batch size gets.
 inline void trim() { check(hades252_trim(), "trim"); }
 inline std::size_t pool_bytes() { return hades252_pool_bytes(); }
