@@ -132,6 +132,11 @@ SIGNATURES = {
     "hades252_cipher_encrypt": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, POINTER(c_uint64), c_void_p]),
     "hades252_cipher_decrypt": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, POINTER(c_uint64), c_void_p,
                                         c_void_p, POINTER(c_size_t)]),
+    "hades252_cipher_perms": (c_size_t, [c_size_t]),
+    "hades252_cipher_encrypt_witness_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, POINTER(c_uint64),
+                                                    c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hades252_cipher_decrypt_witness_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, POINTER(c_uint64),
+                                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hades252_gen_b_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_uint64, c_void_p]),
     "hades252_gen_a_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_void_p]),
     "hades252_digest_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_void_p, c_void_p]),

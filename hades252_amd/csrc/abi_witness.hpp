@@ -1,6 +1,6 @@
-// abi_witness.hpp -- C ABI, device-resident data: gadget witnesses of the sponge (f1) and of Merkle openings (f2), the
-// permutation chains of row f4.  Every argument rule is checked before the device is touched; include/hades252.h holds the
-// contracts.
+// abi_witness.hpp -- C ABI, device-resident data: gadget witnesses of the sponge (f1), of Merkle openings (f2) and of the
+// cipher (f5), the permutation chains of row f4.  Every argument rule is checked before the device is touched;
+// include/hades252.h holds the contracts.
 #pragma once
 
 extern "C" {
@@ -69,6 +69,71 @@ int hades252_merkle_open_witness_dev(const void *d_leaves, const void *d_tree, s
                        (uint8_t *)d_wires, n_perms);
     HIP_TRY(hipGetLastError());
     return HADES252_OK;
+}
+
+}  // extern "C"
+
+// ---- gadget witnesses of the cipher (f5): k_witness_cipher, one message per lane ------------------------------------
+// (after abi_cipher.hpp: its argument rules and fr_mont_of_u64 are reused)
+extern "C" {
+
+// permutations per message of hades252_cipher_*: ceil(M / 4) + 1 for a valid M, else 0
+size_t hades252_cipher_perms(size_t msg_len) {
+    if (msg_len == 0 || msg_len > HADES252_CIPHER_MAX_LEN) return 0;
+    return (msg_len + 3) / 4 + 1;
+}
+
+}  // extern "C"
+
+// the rules of hades252_cipher_*_dev (d_inputs in the place of their required output array) and of the chain witnesses;
+// n > 0.  The side output `side` may be NULL.
+static bool cipher_witness_args_bad(const void *in, const void *keys, const void *nonces, size_t n, size_t len,
+                                    const uint64_t *domain_mont, const void *d_inputs, const void *d_wires, const void *side) {
+    return cipher_args_bad(in, keys, nonces, n, len, domain_mont, d_inputs) || d_wires == nullptr || misaligned(d_wires) ||
+           misaligned(side) || hades252_cipher_perms(len) > kMaxLaunchRecords / n;
+}
+
+// arguments already checked: n >= 1, S * n <= 2^30 (so n, M and S * n pass as 32-bit)
+static int cipher_witness_launch(bool decrypt, const void *d_in, const void *d_keys, const void *d_nonces, size_t n,
+                                 size_t len, const uint64_t domain_mont[4], void *d_inputs, void *d_wires, void *d_out,
+                                 uint8_t *d_ok, int *d_rejected, hipStream_t s) {
+    const Fr dom = fr_from_u64(domain_mont), lw = fr_mont_of_u64(len);
+    const size_t steps = hades252_cipher_perms(len);
+#define HADES_LAUNCH_CIPHER_WITNESS(D)                                                                                   \
+    hipLaunchKernelGGL(k_witness_cipher<D>, dim3(blocks_for(n)), dim3(kBlock), 0, s, (const uint8_t *)d_in,              \
+                       (const uint8_t *)d_keys, (const uint8_t *)d_nonces, (uint32_t)n, (uint32_t)len, (uint32_t)steps,   \
+                       dom, lw, (uint8_t *)d_inputs,                                                                       \
+                       (uint8_t *)d_wires, (uint8_t *)d_out, d_ok, d_rejected)
+    if (decrypt)
+        HADES_LAUNCH_CIPHER_WITNESS(true);
+    else
+        HADES_LAUNCH_CIPHER_WITNESS(false);
+#undef HADES_LAUNCH_CIPHER_WITNESS
+    HIP_TRY(hipGetLastError());
+    return HADES252_OK;
+}
+
+extern "C" {
+
+int hades252_cipher_encrypt_witness_dev(const void *d_msgs, const void *d_keys, const void *d_nonces, size_t n_msgs,
+                                        size_t msg_len, const uint64_t domain_mont[4], void *d_inputs, void *d_wires,
+                                        void *d_ciphers, void *stream) {
+    if (n_msgs == 0) return HADES252_OK;
+    if (cipher_witness_args_bad(d_msgs, d_keys, d_nonces, n_msgs, msg_len, domain_mont, d_inputs, d_wires, d_ciphers))
+        return HADES252_ERR_INVALID_ARG;
+    return cipher_witness_launch(false, d_msgs, d_keys, d_nonces, n_msgs, msg_len, domain_mont, d_inputs, d_wires, d_ciphers,
+                                 nullptr, nullptr, (hipStream_t)stream);
+}
+
+int hades252_cipher_decrypt_witness_dev(const void *d_ciphers, const void *d_keys, const void *d_nonces, size_t n_msgs,
+                                        size_t msg_len, const uint64_t domain_mont[4], void *d_inputs, void *d_wires,
+                                        void *d_msgs, uint8_t *d_ok, int *d_rejected, void *stream) {
+    if (n_msgs == 0) return HADES252_OK;
+    if (cipher_witness_args_bad(d_ciphers, d_keys, d_nonces, n_msgs, msg_len, domain_mont, d_inputs, d_wires, d_msgs) ||
+        misaligned4(d_rejected))
+        return HADES252_ERR_INVALID_ARG;
+    return cipher_witness_launch(true, d_ciphers, d_keys, d_nonces, n_msgs, msg_len, domain_mont, d_inputs, d_wires, d_msgs,
+                                 d_ok, d_rejected, (hipStream_t)stream);
 }
 
 }  // extern "C"

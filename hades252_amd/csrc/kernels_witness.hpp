@@ -205,3 +205,110 @@ __global__ void __launch_bounds__(kBlock) k_witness_path_states(const uint8_t *_
     }
     store_word(inputs + rec * 160 + (size_t)w * 32, v);
 }
+
+// Cipher witness (the construction of k_cipher, kernels_cipher.hpp; CONVENTION UNPINNED): lane i runs message i through
+// S = ceil(M / 4) + 1 permutations, record rec = s * n + i.  inputs[0][i] = [D, M, kx, ky, nonce]; inputs[s][i] (s >= 1) =
+// the output of permutation (s - 1, i) with words 1 + j absorbing word 4 (s - 1) + j of the message: encrypt adds it (the
+// sums are the cipher words), decrypt replaces the state word by the cipher word reduced mod p (a 256-bit word is < 2.2 p:
+// two conditional subtractions), so every input state is canonical, as perm_witness requires.  As in k_witness_sponge the
+// state between steps is the last round's r2 wires in memory, read back by the lane that wrote them.
+//   in   = messages (n x M, encrypt) or ciphers (n x (M + 1), decrypt)
+//   out  = ciphers (n x (M + 1), encrypt) or messages (n x M, decrypt): what k_cipher writes; NULL: not written
+//   ok_out, rejected (decrypt; each may be NULL): the verdict, as k_cipher gives it.  A rejected lane zeroes its message.
+// SGPR budget: the round loop leaves k_witness_sponge's handful of SGPRs to the chain.  So the chain carries the step s
+// (n, M and S * n are below 2^30: 32-bit), n, M and S, the decrypt lane's "every cipher word canonical" bit, and the
+// pointers the rounds write (inputs, wires).  The four pointers of the absorb and the tail are parked in LDS and read back
+// where they are used, behind an opaque index (so not hoisted into registers that live across the rounds).
+struct CipherWitnessPtrs {
+    const uint8_t *in;
+    uint8_t *out, *ok_out;
+    int *rejected;
+};
+
+__device__ __forceinline__ CipherWitnessPtrs cipher_witness_ptrs(const CipherWitnessPtrs *parked) {
+    int z = 0;
+    asm volatile("" : "+s"(z));
+    return parked[z];
+}
+
+template <bool DECRYPT>
+__global__ void __launch_bounds__(kBlock, 3) k_witness_cipher(const uint8_t *__restrict__ in, const uint8_t *__restrict__ keys,
+                                                              const uint8_t *__restrict__ nonces, uint32_t n, uint32_t len,
+                                                              uint32_t steps, Fr domain, Fr len_word,
+                                                              uint8_t *__restrict__ inputs, uint8_t *__restrict__ wires,
+                                                              uint8_t *__restrict__ out, uint8_t *__restrict__ ok_out,
+                                                              int *rejected) {
+    __shared__ CipherWitnessPtrs parked[1];
+    if (threadIdx.x == 0) parked[0] = CipherWitnessPtrs{in, out, ok_out, rejected};
+    __syncthreads();
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool live = i < n;
+    const uint32_t plane = steps * n;
+    const uint32_t in_stride = DECRYPT ? len + 1 : len, out_stride = DECRYPT ? len : len + 1;
+    // step 0's state, parked in the lane's first input record and read back like every later state (the domain, length,
+    // key and nonce hold no registers inside the chain)
+    if (live) {
+        store_word(inputs + i * 160, domain);
+        store_word(inputs + i * 160 + 32, len_word);
+        store_word(inputs + i * 160 + 64, load_word(keys + i * 64));
+        store_word(inputs + i * 160 + 96, load_word(keys + i * 64 + 32));
+        store_word(inputs + i * 160 + 128, load_word(nonces + i * 32));
+    }
+    bool good = true;                                   // decrypt: every cipher word so far canonical
+#pragma unroll 1
+    for (uint32_t s = 0; s < steps; s++) {
+        const size_t rec = (size_t)s * n + i;
+        const uint8_t *src = s == 0 ? inputs + i * 160 : wires + ((size_t)kWitnessLastRow * plane + rec - n) * 32;
+        const size_t stride = s == 0 ? 32 : (size_t)2 * plane * 32;
+        Fr st[5];
+#pragma unroll
+        for (int w = 0; w < 5; w++) st[w] = live ? load_word(src + w * stride) : zero_word();
+        if (s != 0) {                                   // absorb words 4 (s - 1) + j (those < M): the gadget's add gates
+            const CipherWitnessPtrs p = cipher_witness_ptrs(parked);
+            const uint32_t w0 = 4 * (s - 1);
+            const uint8_t *src_w = p.in + (live ? (i * in_stride + w0) * 32 : 0);
+            uint8_t *dst_w = p.out + (live && p.out != nullptr ? (i * out_stride + w0) * 32 : 0);
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                if (w0 + j < len) {
+                    const Fr c = live ? load_word(src_w + j * 32) : zero_word();
+                    Fr o;
+                    if constexpr (DECRYPT) {
+                        good = good && fr_is_canonical(c);
+                        const Fr cr = fr_cond_sub_p(fr_cond_sub_p(c));
+                        o = fr_sub(cr, st[1 + j]);
+                        st[1 + j] = cr;
+                    } else {
+                        st[1 + j] = fr_add(st[1 + j], c);
+                        o = st[1 + j];
+                    }
+                    if (live && p.out != nullptr) store_word(dst_w + j * 32, o);
+                }
+            }
+        }
+        if (live) {
+#pragma unroll
+            for (int w = 0; w < 5; w++) store_word(inputs + rec * 160 + w * 32, st[w]);
+        }
+        F29 y[5];
+        witness_enter(st, y);
+        witness_rounds(y, wires, plane, rec, live);
+    }
+    // the tag: word 1 of the final state, r2[1] of the last round of the lane's last record
+    const CipherWitnessPtrs p = cipher_witness_ptrs(parked);
+    const size_t last = (size_t)(plane - n) + i;
+    const Fr tag = live ? load_word(wires + ((size_t)(kWitnessLastRow + 2) * plane + last) * 32) : zero_word();
+    if constexpr (!DECRYPT) {
+        if (live && p.out != nullptr) store_word(p.out + (i * out_stride + len) * 32, tag);
+    } else {
+        const Fr c = live ? load_word(p.in + (i * in_stride + len) * 32) : zero_word();
+        good = good && fr_is_canonical(c) && fr_eq(c, tag);
+        if (live && !good && p.out != nullptr) {        // a rejected message comes out as M zero words, as from k_cipher
+#pragma unroll 1
+            for (uint32_t k = 0; k < len; k++) store_word(p.out + (i * out_stride + k) * 32, zero_word());
+        }
+        if (live && p.ok_out != nullptr) p.ok_out[i] = good ? 1 : 0;
+        const uint64_t rej = __ballot(live && !good);
+        if ((threadIdx.x & (kWave - 1)) == 0 && rej != 0 && p.rejected != nullptr) atomicAdd(p.rejected, (int)__popcll(rej));
+    }
+}

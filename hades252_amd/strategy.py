@@ -838,6 +838,66 @@ def cipher_decrypt(ciphers_t, keys_t, nonces_t, msg_len: int, domain_mont: int =
     return out, ok, int(rej.item())
 
 
+def cipher_perms(msg_len: int) -> int:
+    """Permutations per message of the cipher (``hades252_cipher_perms``): ceil(msg_len / 4) + 1."""
+    if not 1 <= msg_len <= _lib.CIPHER_MAX_LEN:
+        raise ValueError("cipher_perms: msg_len must be in 1 .. %d (got %d)" % (_lib.CIPHER_MAX_LEN, msg_len))
+    return int(_lib.lib().hades252_cipher_perms(msg_len))
+
+
+def _cipher_witness_buffers(torch, dev, n: int, msg_len: int):
+    S = cipher_perms(msg_len)
+    return (torch.empty((witness_wires(), S, n, 4), dtype=torch.int64, device=dev),
+            torch.empty((S, n, 5, 4), dtype=torch.int64, device=dev))
+
+
+def cipher_encrypt_witness(msgs_t, keys_t, nonces_t, msg_len: int, domain_mont: int = CIPHER_DOMAIN):
+    """Gadget witness of the cipher, encrypt (``hades252_cipher_encrypt_witness_dev``; the arguments of ``cipher_encrypt``).
+    Returns (wires [972, S, n, 4], inputs [S, n, 5, 4], ciphers [n, msg_len + 1, 4]) with S = cipher_perms(msg_len):
+    inputs[s, i] enters permutation s of message i, wires.reshape(972, S * n, 4) == perm_witness(inputs) byte for byte,
+    and the ciphers are those of ``cipher_encrypt``."""
+    import torch
+    kptr, n_keys, dev = _dev_buffer(keys_t, 32, "cipher_encrypt_witness")
+    nptr, n_nonces, ndev = _dev_buffer(nonces_t, 32, "cipher_encrypt_witness")
+    mptr, n_words, mdev = _dev_buffer(msgs_t, 32, "cipher_encrypt_witness")
+    _same_device("cipher_encrypt_witness", dev, ndev, mdev)
+    n = _cipher_shapes("cipher_encrypt_witness", msg_len, n_keys, n_nonces)
+    if n_words != n * msg_len:
+        raise ValueError("cipher_encrypt_witness: buffer is not %d messages of %d scalars" % (n, msg_len))
+    wires, inputs = _cipher_witness_buffers(torch, dev, n, msg_len)
+    out = torch.empty((n, msg_len + 1, 4), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().hades252_cipher_encrypt_witness_dev(mptr, kptr, nptr, n, msg_len, _tag_arr(domain_mont),
+                                                             inputs.data_ptr(), wires.data_ptr(), out.data_ptr(),
+                                                             _stream_ptr(dev)), "cipher_encrypt_witness")
+    return wires, inputs, out
+
+
+def cipher_decrypt_witness(ciphers_t, keys_t, nonces_t, msg_len: int, domain_mont: int = CIPHER_DOMAIN):
+    """Gadget witness of the cipher, decrypt (``hades252_cipher_decrypt_witness_dev``; the arguments of ``cipher_decrypt``).
+    Returns (wires [972, S, n, 4], inputs [S, n, 5, 4], msgs [n, msg_len, 4], ok [n] uint8, n_rejected): the inputs carry
+    the cipher words reduced mod p, so they are canonical for every message; msgs, ok and n_rejected are those of
+    ``cipher_decrypt``.  n_rejected synchronises with the device."""
+    import torch
+    kptr, n_keys, dev = _dev_buffer(keys_t, 32, "cipher_decrypt_witness")
+    nptr, n_nonces, ndev = _dev_buffer(nonces_t, 32, "cipher_decrypt_witness")
+    cptr, n_words, cdev = _dev_buffer(ciphers_t, 32, "cipher_decrypt_witness")
+    _same_device("cipher_decrypt_witness", dev, ndev, cdev)
+    n = _cipher_shapes("cipher_decrypt_witness", msg_len, n_keys, n_nonces)
+    if n_words != n * (msg_len + 1):
+        raise ValueError("cipher_decrypt_witness: buffer is not %d ciphers of %d scalars" % (n, msg_len + 1))
+    wires, inputs = _cipher_witness_buffers(torch, dev, n, msg_len)
+    out = torch.empty((n, msg_len, 4), dtype=torch.int64, device=dev)
+    ok = torch.empty(n, dtype=torch.uint8, device=dev)
+    rej = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().hades252_cipher_decrypt_witness_dev(cptr, kptr, nptr, n, msg_len, _tag_arr(domain_mont),
+                                                             inputs.data_ptr(), wires.data_ptr(), out.data_ptr(),
+                                                             ok.data_ptr(), rej.data_ptr(), _stream_ptr(dev)),
+              "cipher_decrypt_witness")
+    return wires, inputs, out, ok, int(rej.item())
+
+
 def _host_scalars(a, what: str) -> int:
     a = _host_u64(a, what)
     if a.size % 4:

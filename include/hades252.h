@@ -476,6 +476,33 @@ int hades252_cipher_encrypt(const uint64_t *msgs, const uint64_t *keys, const ui
 int hades252_cipher_decrypt(const uint64_t *ciphers, const uint64_t *keys, const uint64_t *nonces, size_t n_msgs,
                             size_t msg_len, const uint64_t domain_mont[4], uint64_t *msgs, uint8_t *ok, size_t *n_rejected);
 
+/* ---- gadget witnesses of the cipher (f5): the third chain of row f4 ---- CONVENTION UNPINNED
+ * The construction of hades252_cipher_*_dev above (and of tests/cipher_model.py), recorded as the chain witnesses record the
+ * sponge and Merkle openings: S = hades252_cipher_perms(M) = ceil(M / 4) + 1 permutations per message (0 for an invalid M),
+ * record rec = s * n + i (step-major), d_inputs receives S * n states of 160 B, d_wires 972 planes of S * n scalars.
+ *   inputs[0][i] = [D, M, kx, ky, nonce]   (M as the field element M, Montgomery form, as the cipher builds it)
+ *   encrypt: inputs[s][i] (s >= 1) = the output of permutation (s - 1, i) with message word 4 (s - 1) + j added to word
+ *            1 + j (the words that exist); these sums are the cipher words.
+ *   decrypt: inputs[s][i] = the output of permutation (s - 1, i) with word 1 + j replaced by cipher word 4 (s - 1) + j
+ *            REDUCED mod p (a 256-bit word is < 2.2 p), so every input state is canonical, accepted message or not.
+ * Defining property: wires == hades252_perm_witness_dev(inputs) byte for byte, the S * n states taken as one flat batch.
+ * Hence the decrypt witness of encrypt(m) is the encrypt witness of m, inputs and wires alike.  Word 1 of the final state
+ * (the tag) is r2[1] of the last round of record (S - 1) n + i.
+ * Side outputs, each may be NULL (not written): encrypt: d_ciphers (n x (M + 1)), byte for byte what
+ * hades252_cipher_encrypt_dev writes; decrypt: d_msgs (n x M), d_ok (n bytes) and *d_rejected (incremented), byte for byte
+ * what hades252_cipher_decrypt_dev gives (a wrong tag or a non-canonical cipher word: M zero words, ok = 0).
+ * One message per lane, the state carried across its steps: one message costs S x the latency of one perm_witness lane.
+ * Rules: those of hades252_cipher_*_dev (the side outputs optional) and of the chain witnesses: n_msgs = 0 is a no-op
+ * success; d_inputs and d_wires must be non-NULL and 16-byte aligned; S * n_msgs must be at most 2^30.  All are checked
+ * before the device is touched. */
+size_t hades252_cipher_perms(size_t msg_len);
+int hades252_cipher_encrypt_witness_dev(const void *d_msgs, const void *d_keys, const void *d_nonces, size_t n_msgs,
+                                        size_t msg_len, const uint64_t domain_mont[4], void *d_inputs, void *d_wires,
+                                        void *d_ciphers, void *stream);
+int hades252_cipher_decrypt_witness_dev(const void *d_ciphers, const void *d_keys, const void *d_nonces, size_t n_msgs,
+                                        size_t msg_len, const uint64_t domain_mont[4], void *d_inputs, void *d_wires,
+                                        void *d_msgs, uint8_t *d_ok, int *d_rejected, void *stream);
+
 /* ---- synthetic inputs and digests (benchmark / verification plumbing) --------------------- */
 /* Generator B: scalar e (global element index first_elem + k) gets 4 splitmix64 limbs, top limb
  * masked to 62 bits (always < p); see DESIGN.md.  Stateless, so shards generate independently. */

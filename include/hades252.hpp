@@ -225,6 +225,25 @@ inline void merkle_open_witness(const void *d_leaves, const void *d_tree, std::s
                                            d_wires, d_bad_count, stream), "merkle_open_witness");
 }
 
+// The cipher's gadget witnesses (same device conventions): S = cipher_perms(msg_len) records per message; the side outputs
+// (ciphers, or messages + verdicts + a device rejection counter) may be nullptr.
+inline std::size_t cipher_perms(std::size_t msg_len) { return hades252_cipher_perms(msg_len); }
+
+inline void cipher_encrypt_witness(const void *d_msgs, const void *d_keys, const void *d_nonces, std::size_t n_msgs,
+                                   std::size_t msg_len, const BlsScalar &domain, void *d_inputs, void *d_wires,
+                                   void *d_ciphers = nullptr, void *stream = nullptr) {
+    check(hades252_cipher_encrypt_witness_dev(d_msgs, d_keys, d_nonces, n_msgs, msg_len, domain.limbs, d_inputs, d_wires,
+                                              d_ciphers, stream), "cipher_encrypt_witness");
+}
+
+inline void cipher_decrypt_witness(const void *d_ciphers, const void *d_keys, const void *d_nonces, std::size_t n_msgs,
+                                   std::size_t msg_len, const BlsScalar &domain, void *d_inputs, void *d_wires,
+                                   void *d_msgs = nullptr, std::uint8_t *d_ok = nullptr, int *d_rejected = nullptr,
+                                   void *stream = nullptr) {
+    check(hades252_cipher_decrypt_witness_dev(d_ciphers, d_keys, d_nonces, n_msgs, msg_len, domain.limbs, d_inputs, d_wires,
+                                              d_msgs, d_ok, d_rejected, stream), "cipher_decrypt_witness");
+}
+
 // What the library caches (pipes: streams, chunk buffers, staging memory) and which kernel a batch size gets.
 inline void trim() { check(hades252_trim(), "trim"); }
 inline std::size_t pool_bytes() { return hades252_pool_bytes(); }
