@@ -71,8 +71,10 @@ extern "C" {
                                      kernel's schedule */
 /* The size rule of HADES252_KERNEL_DEFAULT lives in ONE place, the library: hades252_kernel_for(n) is the selector
  * hades252_perm_batch_dev(.., n_perms = n, ..) runs (never DEFAULT, never LITERAL); hades252_chain_form_for(n) is the form
- * the chain entry points (sponge, streaming absorb, path verification, tree update) and the Merkle levels run for n
- * chains / parents (one of LANES, ROWS, COOP, FAST -- the per-state arithmetic of that kernel); hades252_kernel_name gives
+ * the chain entry points (sponge, streaming absorb, path verification, tree update) run for n chains, and a full Merkle
+ * level for n parents (one of LANES, ROWS, COOP, FAST -- the per-state arithmetic of that kernel).  Two exceptions: a
+ * ragged level of 4 097 .. 16 384 parents runs FAST (COOP takes full levels only), and a tree build or root may run
+ * several full levels of arity 2 or 4 in one fused COOP launch (k_merkle_coop), the smaller ones included; hades252_kernel_name gives
  * the name of the __global__ function a profiler shows for a selector and batch size ("k_perm_fast", "k_perm_lanes", ..;
  * NULL for an unknown selector). */
 int hades252_kernel_for(size_t n_perms);

@@ -1,19 +1,23 @@
 """Helpers shared by the GPU-tier test files (tests/test_gpu_*.py, one file per SURVEY section 8 row).  The fixtures
 `torch_cuda` and `H` live in conftest.py."""
 import os
+import random
 import sys
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import hades_spec as S  # noqa: E402
-from oracle_lib import limbs_of, int_of  # noqa: E402
+from oracle_lib import P, R, limbs_of, int_of  # noqa: E402
 from test_blob_kat import ARK_SHA256, MDS_SHA256, blob_bytes  # noqa: E402,F401
 
 __all__ = ["KERNELS", "TAG", "TAG4", "CAP", "SITES_PERM", "to_dev", "to_host", "hex_of", "scalars_dev", "rows",
            "kernel_available", "each_state_is_input_or_output", "_record", "word_boundary_values", "ARK_SHA256", "MDS_SHA256",
-           "blob_bytes"]
+           "blob_bytes", "EDGE_VALUES", "edge_scalars", "SENTINEL", "Guarded", "guarded_call", "FORM_SIZES", "LEVEL_SIZES",
+           "sponge_form", "absorb_form", "level_form", "verify_form", "update_form", "form_family", "oracle_sponge_var",
+           "SPONGE_BUCKETS", "COUNT_GRID_RECORDS"]
 
 KERNELS = [1, 2, 3, 4, 5]   # HADES252_KERNEL_LITERAL, _FAST (one state per lane), _COOP (five waves per state), _LANES (one
                             # state per wave, elements spread over 16-lane rows), _ROWS (one state per row, four per wave)
@@ -81,3 +85,164 @@ def word_boundary_values():
     out += [(1 << 255, False), ((1 << 256) - 1, False), (p, False), (p - 1, True), (0, True)]
     assert all((v < p) == ok for v, ok in out)
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# edge values: the field elements where a modular add / reduce goes wrong (shared by the perm, sponge and Merkle tiers)
+# ---------------------------------------------------------------------------------------------
+EDGE_VALUES = [0, 1, 2, P - 1, P - 2, R, P - R, (1 << 255) % P, (1 << 254) - 1, 0xFFFFFFFF, P - (1 << 32),
+               0xFFFFFFFF00000000, (P - 1) // 2, (1 << 128) - 1]
+
+
+def edge_scalars(n, seed, edge_ratio=0.5):
+    """n canonical scalars (4 uint64 limbs each, flat): each one an EDGE_VALUES entry with probability edge_ratio, else
+    uniform-ish below p (random low limbs, top limb below p's).  Used as Montgomery words directly (every canonical value
+    is one)."""
+    rng = np.random.default_rng(seed)
+    tab = np.array([limbs_of(v) for v in EDGE_VALUES], dtype=np.uint64)
+    out = rng.integers(0, 1 << 64, size=(n, 4), dtype=np.uint64, endpoint=False)
+    out[:, 3] %= np.uint64(P >> 192)
+    edge = rng.random(n) < edge_ratio
+    out[edge] = tab[rng.integers(0, len(EDGE_VALUES), size=int(edge.sum()))]
+    return out.reshape(-1)
+
+
+# ---------------------------------------------------------------------------------------------
+# guarded outputs: the kernel writes into the interior of a buffer whose guard rows (before and after) and interior start
+# out as the non-canonical sentinel 2^256 - 1 (every word above p: no result equals it)
+# ---------------------------------------------------------------------------------------------
+SENTINEL = -1          # int64 view of 0xFFFF_FFFF_FFFF_FFFF
+GUARD_ROWS = 64        # 32-byte rows on each side (2 KiB)
+
+
+class Guarded:
+    """A device buffer [GUARD_ROWS | interior | GUARD_ROWS] of int64, all SENTINEL; `.t` is the interior in `shape`
+    (the last dimension a multiple of 4 limbs).  `init` (optional) is copied into the interior (in-place kernels)."""
+
+    def __init__(self, torch, shape, init=None):
+        self.torch = torch
+        n = int(np.prod(shape))
+        assert n % 4 == 0
+        g = GUARD_ROWS * 4
+        self.buf = torch.full((g + n + g,), SENTINEL, dtype=torch.int64, device="cuda")
+        self.g, self.n = g, n
+        self.t = self.buf[g:g + n].view(*shape)
+        if init is not None:
+            self.t.copy_(init.reshape(shape))
+
+    @property
+    def ptr(self):
+        return self.t.data_ptr()
+
+    def check(self, what="", interior=True):
+        """The guards are intact and (interior) no 32-byte word of the interior still holds the sentinel."""
+        self.torch.cuda.synchronize()
+        g = self.g
+        assert bool((self.buf[:g] == SENTINEL).all()) and bool((self.buf[g + self.n:] == SENTINEL).all()), \
+            "guard row overwritten %s" % (what,)
+        if not interior:
+            return self.t
+        left = int((self.buf[g:g + self.n].view(-1, 4) == SENTINEL).all(dim=1).sum().item())
+        assert left == 0, "%d interior word(s) never written %s" % (left, what)
+        return self.t
+
+
+def guarded_call(torch, shape, call, what=""):
+    """Run `call(ptr)` (a C-ABI call through hades_lib returning its status) on the interior of a fresh Guarded buffer;
+    assert the status is 0, the guards are intact and every interior word was written.  Returns the interior."""
+    g = Guarded(torch, shape)
+    rc = call(g.ptr)
+    assert rc == 0, "status %d %s" % (rc, what)
+    return g.check(what)
+
+
+# ---------------------------------------------------------------------------------------------
+# which kernel runs: a mirror of the size dispatch of abi_sponge.hpp, abi_merkle.hpp and launch.hpp (tests/test_chain_forms.py
+# checks it against the library's exported size rule; the GPU tests assert that their sizes reach every form they claim)
+# ---------------------------------------------------------------------------------------------
+LANES_HELPED_MAX, LANES_MAX, ROWS_MAX, COOP_MAX = 768, 1 << 10, 1 << 12, 1 << 14
+SPONGE_BUCKETS = 1024                # counting-sort buckets (the last one takes every longer message)
+COUNT_GRID_RECORDS = 2048 * 256      # k_sponge_count's grid cap: larger batches take a second grid-stride trip
+
+
+def _chain(n, lanes, rows, coop, lane):
+    if n <= LANES_HELPED_MAX:
+        return lanes % "true"
+    if n <= LANES_MAX:
+        return lanes % "false"
+    if n <= ROWS_MAX:
+        return rows
+    if n <= COOP_MAX:
+        return coop
+    return lane
+
+
+def sponge_form(n, sorted=False):
+    """The kernels hades252_sponge_hash[_var_ex]_dev launches for n messages, in launch order (the chain kernel last).
+    `sorted`: scratch was given -- the device sort runs only above COOP_MAX messages."""
+    chain = _chain(n, "k_sponge_lanes<%s>", "k_sponge_rows", "k_sponge_coop", "k_sponge")
+    if sorted and n > COOP_MAX:
+        return ("k_sponge_count", "k_sponge_scan", "k_sponge_scatter", chain)
+    return (chain,)
+
+
+def absorb_form(n):
+    """The kernel hades252_sponge_absorb_dev runs for n states."""
+    return _chain(n, "k_sponge_absorb_lanes<%s>", "k_sponge_absorb_rows", "k_sponge_absorb_coop", "k_sponge_absorb")
+
+
+def level_form(n_children, arity):
+    """The kernel one level of n_children children runs (hades252_merkle_level_pad_dev, and every unfused level of a tree):
+    a ragged level of COOP_MAX or fewer parents above ROWS_MAX runs one parent per lane, not five waves per parent."""
+    n = -(-n_children // arity)
+    if n <= LANES_MAX:
+        return "k_merkle_lanes<%d, %s>" % (arity, "true" if n <= LANES_HELPED_MAX else "false")
+    if n <= ROWS_MAX:
+        return "k_merkle_rows<%d>" % arity
+    if n <= COOP_MAX and n_children % arity == 0:
+        return "k_merkle_coop<%d>" % arity
+    return "k_merkle_level_fast<%d>" % arity
+
+
+def verify_form(nq, arity):
+    """The kernel hades252_merkle_verify_dev runs for nq queries."""
+    return _chain(nq, "k_merkle_verify_lanes<%d, %%s>" % arity, "k_merkle_verify_rows<%d>" % arity,
+                  "k_merkle_verify_coop<%d>" % arity, "k_merkle_verify<%d>" % arity)
+
+
+def update_form(nu, arity):
+    """The kernel hades252_merkle_update_dev runs for nu updates on a level of more than nu parents (a level with no more
+    parents than updates is recomputed whole, by level_form)."""
+    return _chain(nu, "k_merkle_update_lanes<%d, %%s>" % arity, "k_merkle_update_rows<%d>" % arity,
+                  "k_merkle_update_coop<%d>" % arity, "k_merkle_update_fast<%d>" % arity)
+
+
+def form_family(name):
+    """"lanes" / "rows" / "coop" / "fast": the per-state arithmetic of a chain kernel (hades252_chain_form_for's answer)."""
+    base = name.split("<")[0]
+    for fam in ("lanes", "rows", "coop"):
+        if base.endswith("_" + fam):
+            return fam
+    return "fast"
+
+
+# One size list per form (chains, messages, states, queries, updates, or parents of a level): first size, a ragged size
+# inside, last size.  The one-chain-per-lane form has no last size: its third entry is a second ragged size.
+FORM_SIZES = {"lanes_helped": (1, 386, 768), "lanes": (769, 901, 1024), "rows": (1025, 2051, 4096),
+              "coop": (4097, 9001, 16384), "fast": (16385, 17003, 20011)}
+# Levels: the coop form takes full levels only; the per-lane one also every ragged level above ROWS_MAX parents
+LEVEL_SIZES = dict(FORM_SIZES, fast_ragged=(4097, 9001, 16384))
+
+
+def oracle_sponge_var(oracle, pool, offsets, lengths, cap, pad, threads=16):
+    """oracle.sponge_var over chunks on host threads (the C oracle is single-threaded per call and releases the GIL)."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    lengths = np.ascontiguousarray(lengths, dtype=np.uint64)
+    n = offsets.size
+    if n == 0:
+        return np.zeros(0, dtype=np.uint64)
+    step = -(-n // threads)
+    with ThreadPoolExecutor(threads) as ex:
+        parts = list(ex.map(lambda a: oracle.sponge_var(pool, offsets[a:a + step], lengths[a:a + step], cap, pad),
+                            range(0, n, step)))
+    return np.concatenate(parts)

@@ -100,8 +100,7 @@ def test_edge_values(torch_cuda, hades_lib, H, oracle, kernel):
     if not kernel_available(hades_lib, torch, kernel):
         pytest.skip("kernel %d not built" % kernel)
     rng = random.Random(1)
-    edge = [0, 1, 2, P - 1, P - 2, R, P - R, (1 << 255) % P, (1 << 254) - 1, 0xFFFFFFFF, P - (1 << 32),
-            0xFFFFFFFF00000000, (P - 1) // 2, 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFF]
+    edge = EDGE_VALUES
     states = []
     for _ in range(2048):
         states.append([rng.choice(edge) if rng.random() < 0.7 else rng.randrange(P) for _ in range(5)])
@@ -116,8 +115,7 @@ def test_exhaustive_edge_tuples(torch_cuda, H, oracle):
     states, shipped kernel vs the CPU oracle, all bits."""
     import itertools
     torch = torch_cuda
-    edge = [0, 1, 2, P - 1, P - 2, R, P - R, (1 << 255) % P, (1 << 254) - 1, 0xFFFFFFFF, P - (1 << 32),
-            0xFFFFFFFF00000000, (P - 1) // 2, (1 << 128) - 1]
+    edge = EDGE_VALUES
     tab = np.array([limbs_of(v) for v in edge], dtype=np.uint64)
     idx = np.array(list(itertools.product(range(len(edge)), repeat=5)), dtype=np.int64)
     inp = np.ascontiguousarray(tab[idx]).reshape(-1)

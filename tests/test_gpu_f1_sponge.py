@@ -89,23 +89,25 @@ def test_sponge_var_equals_fixed_and_packed(torch_cuda, H, oracle):
 
 
 @pytest.mark.parametrize("pad", [0, 1])
-def test_sponge_sorted_equals_unsorted_and_oracle(torch_cuda, H, oracle, pad):
-    """Ragged lengths (0 .. 70 scalars, a few very long, one beyond the last sort bucket): the device-sorted run gives
-    the same digests in message order as the plain run and the oracle."""
+def test_sponge_sorted_equals_unsorted_and_oracle(torch_cuda, hades_lib, H, oracle, pad):
+    """Ragged lengths (0 .. 70 scalars, a few very long, one beyond the last sort bucket): the device-sorted run (above
+    COOP_MAX messages, so that the sort runs; guarded digests, zero-filled scratch) gives the same digests in message
+    order as the plain run and the oracle."""
     torch = torch_cuda
     rng = random.Random(77 + pad)
-    n = 5000
+    n = 17000
+    assert sponge_form(n, sorted=True)[0] == "k_sponge_count"
     lens = [rng.choice([0, 1, 3, 4, 5, 8, 9, 17, 33, 70]) if rng.random() < 0.8 else rng.randrange(0, 40) for _ in range(n)]
     lens[123] = 4 * 1030                                     # > 1023 blocks: clamps into the last bucket
     lens[4000] = 600
     offs = np.cumsum([0] + lens[:-1]).astype(np.uint64)
     pool = oracle.gen_b(8, int(sum(lens)) + 1)
     lens_a = np.array(lens, dtype=np.uint64)
-    exp = oracle.sponge_var(pool, offs, lens_a, CAP, pad)
+    exp = oracle_sponge_var(oracle, pool, offs, lens_a, CAP, pad)
     dp, do, dl = to_dev(torch, pool).view(-1, 4), to_dev(torch, offs), to_dev(torch, lens_a)
     plain = to_host(H.sponge_hash_var(dp, do, dl, CAP, pad))
-    srt = to_host(H.sponge_hash_var(dp, do, dl, CAP, pad, sort=True))
-    assert (plain == exp).all() and (srt == exp).all()
+    srt, nb = _sponge_var_dev(torch, hades_lib, dp, pool.size // 4, offs, lens_a, CAP, pad, sort=True)
+    assert (plain == exp).all() and (srt.reshape(-1) == exp).all() and nb == 0
     # tiny batches and n not a multiple of the block size
     for m in (1, 2, 63, 65, 257):
         e = oracle.sponge_var(pool, offs[:m], lens_a[:m], CAP, pad)
@@ -181,7 +183,8 @@ def test_small_batch_sponge_one_message_per_wave(torch_cuda, hades_lib, H, oracl
         got = to_host(H.sponge_hash_var(dp, to_dev(torch, oa), to_dev(torch, la), CAP, pad))
         assert (got == exp).all(), n
         if n in (3, 768, 1024, 5000, 16385):
-            assert (to_host(H.sponge_hash_var(dp, to_dev(torch, oa), to_dev(torch, la), CAP, pad, sort=True)) == exp).all()
+            srt, nb = _sponge_var_dev(torch, hades_lib, dp, 3000, oa, la, CAP, pad, sort=True)
+            assert (srt.reshape(-1) == exp).all() and nb == 0, n
     # one long message (750 blocks): the chain of dependent permutations the low-latency form is for
     one = oracle.sponge_var(pool, np.array([0], dtype=np.uint64), np.array([2999], dtype=np.uint64), CAP, pad)
     assert (to_host(H.sponge_hash_var(dp, to_dev(torch, np.array([0], dtype=np.uint64)),
@@ -243,3 +246,243 @@ def test_sponge_golden_vectors_on_the_device(torch_cuda, H, oracle, kat):
         host = to_host(got).reshape(-1, 4)
         for i, v in enumerate(vs):
             assert int_of(host[i]) == int(v["digest_mont"], 16), v
+
+
+# ---------------------------------------------------------------------------------------------
+# every kernel form, guarded outputs, edge values, bad messages, the device sort (tests/gpu_common.py: form table, sizes)
+# ---------------------------------------------------------------------------------------------
+M64 = (1 << 64) - 1
+# messages that share one trip count in each form: the three of a helped block, one per wave (four waves a block)
+# unhelped, the four of a wave in rows, the 64 of a block in coop, the 64 of a wave in the per-lane kernel
+GROUP = {"lanes_helped": 3, "lanes": 4, "rows": 4, "coop": 64, "fast": 64}
+FORM_KERNEL = {"lanes_helped": "k_sponge_lanes<true>", "lanes": "k_sponge_lanes<false>", "rows": "k_sponge_rows",
+               "coop": "k_sponge_coop", "fast": "k_sponge"}
+CAPS = [P - 1, 0, R]
+
+
+def _cap(v):
+    return (ctypes.c_uint64 * 4)(*limbs_of(v))
+
+
+def _sponge_var_dev(torch, hades_lib, dpool, n_scalars, offs, lens, cap, pad, sort=False):
+    """hades252_sponge_hash_var_ex_dev into a guarded digest buffer.  sort: scratch of exactly
+    hades252_sponge_sort_scratch_bytes(n), zero-filled (a slot never written then names message 0, inside the batch), and
+    a guard after it.  Returns (digests [n, 4] uint64, bad count)."""
+    n = len(offs)
+    do, dl = to_dev(torch, np.asarray(offs, dtype=np.uint64)), to_dev(torch, np.asarray(lens, dtype=np.uint64))
+    bad = torch.zeros(1, dtype=torch.int32, device="cuda")
+    sptr, sbytes, scr = None, 0, None
+    if sort:
+        sbytes = hades_lib.hades252_sponge_sort_scratch_bytes(n)
+        scr = torch.full((sbytes + 256,), 0xA5, dtype=torch.uint8, device="cuda")
+        scr[:sbytes].zero_()
+        sptr = scr.data_ptr()
+    got = guarded_call(torch, (n, 4), lambda ptr: hades_lib.hades252_sponge_hash_var_ex_dev(
+        dpool.data_ptr(), n_scalars, do.data_ptr(), dl.data_ptr(), n, _cap(cap), pad, ptr, bad.data_ptr(), sptr, sbytes,
+        None), "sponge n=%d sort=%s" % (n, sort))
+    if sort:
+        assert bool((scr[sbytes:] == 0xA5).all()), "write past the sort scratch"
+    return to_host(got).reshape(n, 4), int(bad.item())
+
+
+def _trip_layout(n, group, rng, short=(0, 1, 2, 3, 4, 5, 7, 8, 9, 12, 17)):
+    """Ragged lengths with three patterns aligned to the form's group boundaries, at the start and in the middle of the
+    batch: one long message among short ones, an all-empty group, a group of lengths 0..3 around the pad boundary."""
+    lens = [rng.choice(short) for _ in range(n)]
+    for base in (0, group * (n // group // 2)):
+        if base + 3 * group > n:
+            continue
+        lens[base:base + group] = [1] * group
+        lens[base + group // 2] = 33
+        lens[base + group:base + 2 * group] = [0] * group
+        lens[base + 2 * group:base + 3 * group] = [i % 4 for i in range(group)]
+    return lens
+
+
+def _bad_messages(n, n_pool):
+    """(index, offset, length) of messages that do not lie inside a pool of n_pool scalars, and one that does (an empty
+    message at the very end), for a batch of n >= 16."""
+    return [(n // 7, n_pool - 2, 8),                 # runs past the end
+            (n // 5, n_pool + 1, 4),                 # starts past the end
+            (n // 3, n_pool + 1, 0),                 # starts past the end, empty
+            (n // 2, M64 - 2, 8),                    # offset + length wraps past 2^64
+            (n - 3, 5, M64),                         # length near 2^64 (len + 4 wraps in the sort's bucket)
+            (n - 1, 0, M64 - 3)], (n - 2, n_pool, 0)
+
+
+@pytest.mark.parametrize("pad", [0, 1])
+@pytest.mark.parametrize("form", list(FORM_SIZES))
+def test_sponge_var_every_form_edges_trips_and_bad_messages(torch_cuda, hades_lib, oracle, form, pad):
+    """Every form at its first, ragged and last size: trip-count patterns on its group boundaries, edge-value pool and
+    capacity (p-1, 0, R), out-of-pool messages counted exactly and hashed as the empty message, every other digest
+    equal to the oracle; plain and with sort scratch (the sort runs only in the per-lane form)."""
+    torch = torch_cuda
+    rng = random.Random("%s/%d" % (form, pad))
+    n_pool = 4000
+    pool = edge_scalars(n_pool, 31 + pad)
+    dp = to_dev(torch, pool).view(-1, 4)
+    empty = {}
+    for k, n in enumerate(FORM_SIZES[form]):
+        assert sponge_form(n) == (FORM_KERNEL[form],)
+        cap = CAPS[k % 3]
+        lens = _trip_layout(n, GROUP[form], rng)
+        offs = [rng.randrange(0, n_pool - l + 1) for l in lens]
+        n_bad = 0
+        if n >= 16:
+            bads, good_end = _bad_messages(n, n_pool)
+            for i, o, l in bads:
+                offs[i], lens[i] = o, l
+            offs[good_end[0]], lens[good_end[0]] = good_end[1], good_end[2]
+            n_bad = len(bads)
+        oa, la = np.array(offs, dtype=np.uint64), np.array(lens, dtype=np.uint64)
+        bad_mask = (oa > n_pool) | (la > np.uint64(n_pool) - np.minimum(oa, np.uint64(n_pool)))
+        assert int(bad_mask.sum()) == n_bad
+        so, sl = oa.copy(), la.copy()
+        so[bad_mask], sl[bad_mask] = 0, 0
+        exp = oracle_sponge_var(oracle, pool, so, sl, cap, pad).reshape(n, 4)
+        if cap not in empty:
+            empty[cap] = oracle.sponge_var(pool, np.zeros(1, np.uint64), np.zeros(1, np.uint64), cap, pad).reshape(4)
+        assert (exp[bad_mask] == empty[cap]).all()
+        for sort in (False, True):
+            got, nb = _sponge_var_dev(torch, hades_lib, dp, n_pool, oa, la, cap, pad, sort)
+            assert nb == n_bad, (form, n, sort, nb)
+            assert (got == exp).all(), (form, n, sort, np.flatnonzero((got != exp).any(axis=1))[:10])
+
+
+@pytest.mark.parametrize("form", list(FORM_SIZES))
+def test_sponge_fixed_length_every_form(torch_cuda, hades_lib, oracle, form):
+    """hades252_sponge_hash_dev, lengths 1..16 (those = 0 mod 4 take an extra block with pad mode 1), edge-value messages
+    and capacity, into guarded digests, vs the oracle."""
+    torch = torch_cuda
+    n = FORM_SIZES[form][0 if form in ("coop", "fast") else 1]
+    assert sponge_form(n) == (FORM_KERNEL[form],)
+    for length in (1, 2, 3, 4, 5, 7, 8, 9, 16):
+        msgs = edge_scalars(n * length, 1000 * length + n)
+        dm = to_dev(torch, msgs)
+        for pad in (0, 1):
+            cap = CAPS[(length + pad) % 3]
+            exp = oracle_sponge_var(oracle, msgs, np.arange(n, dtype=np.uint64) * np.uint64(length),
+                                    np.full(n, length, dtype=np.uint64), cap, pad).reshape(n, 4)
+            got = guarded_call(torch, (n, 4), lambda ptr: hades_lib.hades252_sponge_hash_dev(
+                dm.data_ptr(), n, length, _cap(cap), pad, ptr, None), (form, length, pad))
+            assert (to_host(got).reshape(n, 4) == exp).all(), (form, length, pad)
+
+
+def _occupied_buckets(lens, pad):
+    b = (np.asarray(lens, dtype=np.uint64) + np.uint64(pad + 3)) // np.uint64(4)     # wraps like the kernel's
+    b = np.maximum(b, np.uint64(1))
+    return np.minimum(b, np.uint64(SPONGE_BUCKETS - 1)).astype(np.int64)
+
+
+def _sort_case(case, pad, rng):
+    """(lengths, pool size) of the four sorted-batch cases, each above COOP_MAX messages."""
+    if case == "one_bucket":
+        return [5] * 20000, 64
+    if case == "every_bucket":                        # buckets 1 .. 1023, one long message each, the rest short
+        lens = [rng.randrange(0, 13) for _ in range(20000)]
+        pos = rng.sample(range(20000), SPONGE_BUCKETS - 1)
+        for b, i in enumerate(pos, 1):
+            lens[i] = 4 * b - pad
+        return lens, 4 * SPONGE_BUCKETS
+    if case == "clamp":                               # > 1022 blocks: the last bucket; 4088 moves bucket with the pad mode
+        lens = [rng.randrange(0, 13) for _ in range(17000)]
+        for i in rng.sample(range(17000), 27):
+            lens[i] = rng.choice([4084, 4085, 4087, 4088, 4089, 4091, 4092, 4096, 4120])
+        return lens, 4200
+    n = COUNT_GRID_RECORDS + 1037                     # k_sponge_count takes a second grid-stride trip
+    return np.random.default_rng(7 + pad).integers(0, 13, size=n), 64
+
+
+@pytest.mark.parametrize("pad", [0, 1])
+@pytest.mark.parametrize("case", ["one_bucket", "every_bucket", "clamp", "strided_count"])
+def test_sponge_device_sort_cases(torch_cuda, hades_lib, oracle, case, pad):
+    """The counting sort (k_sponge_count / _scan / _scatter) in front of k_sponge: sorted digests == unsorted k_sponge
+    digests for the whole batch (each in its own guarded buffer, zero-filled scratch with a guard after it) == the oracle
+    (whole batch up to ~20 000 messages, else the first and last message of every occupied bucket + 3 000 random)."""
+    torch = torch_cuda
+    rng = random.Random("%s/%d" % (case, pad))
+    lens, n_pool = _sort_case(case, pad, rng)
+    n = len(lens)
+    assert sponge_form(n, sorted=True) == ("k_sponge_count", "k_sponge_scan", "k_sponge_scatter", "k_sponge")
+    buckets = _occupied_buckets(lens, pad)
+    occ = np.unique(buckets)
+    if case == "one_bucket":
+        assert occ.size == 1
+    elif case == "every_bucket":
+        assert occ.size == SPONGE_BUCKETS - 1 and occ.size > 64
+    elif case == "clamp":
+        assert (buckets == SPONGE_BUCKETS - 1).sum() >= 10 and max(lens) > 4 * (SPONGE_BUCKETS - 1)
+    else:
+        assert n > COUNT_GRID_RECORDS
+    pool = edge_scalars(n_pool + 8, 77 + pad)
+    la = np.array(lens, dtype=np.uint64)
+    oa = np.array([rng.randrange(0, n_pool - int(l) + 1) for l in lens], dtype=np.uint64) if n <= 20000 else \
+        np.random.default_rng(3).integers(0, n_pool - 12, size=n).astype(np.uint64)
+    dp = to_dev(torch, pool).view(-1, 4)
+    cap = CAPS[pad]
+    plain, nb0 = _sponge_var_dev(torch, hades_lib, dp, n_pool + 8, oa, la, cap, pad, sort=False)
+    srt, nb1 = _sponge_var_dev(torch, hades_lib, dp, n_pool + 8, oa, la, cap, pad, sort=True)
+    assert nb0 == nb1 == 0
+    diff = np.flatnonzero((plain != srt).any(axis=1))
+    assert diff.size == 0, (case, diff.size, diff[:10])
+    if n <= 20000:
+        sample = np.arange(n)
+    else:
+        firsts = [int(np.flatnonzero(buckets == b)[0]) for b in occ] + [int(np.flatnonzero(buckets == b)[-1]) for b in occ]
+        sample = np.unique(np.concatenate([np.array(firsts), np.random.default_rng(11).integers(0, n, size=3000), [0, n - 1]]))
+    exp = oracle_sponge_var(oracle, pool, oa[sample], la[sample], cap, pad).reshape(-1, 4)
+    assert (plain[sample] == exp).all(), case
+
+
+@pytest.mark.parametrize("form", list(FORM_SIZES))
+def test_streaming_every_form_guarded(torch_cuda, hades_lib, oracle, form):
+    """init / absorb / squeeze in every absorb form (the per-lane k_sponge_absorb above COOP_MAX states), on guarded
+    in-place state buffers: one call == two calls == block by block (whole states); one absorb of an edge-value block ==
+    oracle perm([capacity, 0 + block]) on every word; squeeze(w), w = 0..4; blocks_each = 0 is a no-op."""
+    torch = torch_cuda
+    lib = hades_lib
+    n, t = FORM_SIZES[form][1], 3
+    kern = {"lanes_helped": "k_sponge_absorb_lanes<true>", "lanes": "k_sponge_absorb_lanes<false>",
+            "rows": "k_sponge_absorb_rows", "coop": "k_sponge_absorb_coop", "fast": "k_sponge_absorb"}[form]
+    assert absorb_form(n) == kern
+    cap = CAPS[len(form) % 3]
+    blocks = edge_scalars(n * t * 4, 500 + n)
+    db = to_dev(torch, blocks).view(n, t, 4, 4)
+
+    def fresh():
+        g = Guarded(torch, (n, 5, 4))
+        assert lib.hades252_sponge_init_dev(g.ptr, n, _cap(cap), None) == 0
+        g.check("init")
+        return g
+
+    def absorb(g, blk, each):
+        assert lib.hades252_sponge_absorb_dev(g.ptr, blk.data_ptr(), n, each, None) == 0
+        g.check("absorb")
+
+    a = fresh()
+    absorb(a, db, t)
+    b = fresh()
+    absorb(b, db[:, :1].contiguous(), 1)
+    absorb(b, db[:, 1:].contiguous(), t - 1)
+    c = fresh()
+    for i in range(t):
+        absorb(c, db[:, i].contiguous(), 1)
+    assert torch.equal(a.t, b.t) and torch.equal(a.t, c.t)
+    before = a.t.clone()
+    absorb(a, db, 0)
+    assert torch.equal(a.t, before)
+    # squeeze every word, into guarded digests
+    for w in range(5):
+        got = guarded_call(torch, (n, 4), lambda ptr: lib.hades252_sponge_squeeze_dev(a.ptr, ptr, n, w, None), ("squeeze", w))
+        assert torch.equal(got, a.t[:, w]), w
+    # the digest word == the one-shot sponge without padding over the same scalars
+    exp = oracle_sponge_var(oracle, blocks, np.arange(n, dtype=np.uint64) * np.uint64(4 * t),
+                            np.full(n, 4 * t, dtype=np.uint64), cap, 0).reshape(n, 4)
+    assert (to_host(a.t[:, 1]).reshape(n, 4) == exp).all()
+    # one absorb of one block: every word == perm([capacity, 0 + block])
+    d = fresh()
+    absorb(d, db[:, 0].contiguous(), 1)
+    st = np.zeros((n, 5, 4), dtype=np.uint64)
+    st[:, 0] = np.array(limbs_of(cap), dtype=np.uint64)
+    st[:, 1:] = blocks.reshape(n, t, 4, 4)[:, 0]
+    assert (to_host(d.t) == oracle.perm_batch(st.reshape(-1))).all()

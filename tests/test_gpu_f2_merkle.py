@@ -22,6 +22,10 @@ from gpu_common import *  # noqa: E402,F401,F403  (helpers shared by the GPU tie
 pytestmark = pytest.mark.gpu
 
 
+def _tag(v):
+    return (ctypes.c_uint64 * 4)(*limbs_of(v))
+
+
 def test_merkle(torch_cuda, H, oracle, kat):
     torch = torch_cuda
     g = kat["merkle4_root_mont"]
@@ -216,11 +220,16 @@ def test_merkle_verify_2pow16_queries(torch_cuda, H, oracle):
 
 
 @pytest.mark.parametrize("arity", [1, 2, 3, 4])
-def test_small_batch_verify_one_query_per_wave(torch_cuda, H, oracle, arity):
+def test_small_batch_verify_one_query_per_wave(torch_cuda, hades_lib, H, oracle, arity):
     """The same openings verified one per wave (<= 1024 queries, both forms) and one per lane (> 1024) give the same roots;
-    tampered siblings are caught."""
+    tampered siblings are caught.  Every prefix is verified into its own guarded, sentinel-filled buffer."""
     torch = torch_cuda
     tag = TAG[arity]
+
+    def verify_into_guarded(lv, idx, paths, m, depth):
+        pptr = paths.data_ptr() if paths.numel() else None
+        return guarded_call(torch, (m, 4), lambda ptr: hades_lib.hades252_merkle_verify_dev(
+            lv.data_ptr(), idx.data_ptr(), pptr, m, depth, arity, _tag(tag), 1, ptr, None), ("verify", m))
     if arity == 1:
         chain = H.gen_b(17000, "cuda")
         z = torch.zeros(17000, dtype=torch.int64, device="cuda")
@@ -231,7 +240,7 @@ def test_small_batch_verify_one_query_per_wave(torch_cuda, H, oracle, arity):
             cur = oracle.merkle_level(cur, 1, tag, 1)
         assert (to_host(ref[:50]) == cur).all()
         for m in (1, 3, 768, 769, 1024, 1025, 4096, 4097, 16384):
-            assert torch.equal(H.merkle_verify(chain[:m].contiguous(), z[:m].contiguous(), e[:m].contiguous(), 1, tag, 1), ref[:m])
+            assert torch.equal(verify_into_guarded(chain[:m].contiguous(), z[:m].contiguous(), e[:m].contiguous(), m, 6), ref[:m])
         return
     n_leaves = arity ** 7 + 5
     depth = H.merkle_depth(n_leaves, arity)
@@ -247,7 +256,7 @@ def test_small_batch_verify_one_query_per_wave(torch_cuda, H, oracle, arity):
     ref = H.merkle_verify(lv, idx, paths, arity, tag, 1)                      # 17 000 queries: one per lane
     assert bool((ref == tree[-1:]).all())
     for m in (1, 2, 3, 4, 767, 768, 769, 1024, 1025, 1026, 4095, 4096, 4097, 5000, 16384, 16385):   # per wave / row / five waves / lane
-        r = H.merkle_verify(lv[:m].contiguous(), idx[:m].contiguous(), paths[:m].contiguous(), arity, tag, 1)
+        r = verify_into_guarded(lv[:m].contiguous(), idx[:m].contiguous(), paths[:m].contiguous(), m, depth)
         assert torch.equal(r, ref[:m]), m
     bad = paths[:5].clone()
     bad[2, depth // 2, 0, 1] ^= 4
@@ -407,3 +416,153 @@ def test_config4_merkle_2pow24(torch_cuda, H, oracle, kat):
     sub = 1 << 20
     exp = oracle.merkle4_root(oracle.gen_b(0, sub), tag, 1)
     assert (to_host(H.merkle4_root(leaves[:sub], tag, 1)) == exp).all()
+
+
+# ---------------------------------------------------------------------------------------------
+# every kernel form with edge values, into guarded outputs (tests/gpu_common.py: form table, size lists, Guarded)
+# ---------------------------------------------------------------------------------------------
+LEVEL_KERNEL = {"lanes_helped": "k_merkle_lanes<%d, true>", "lanes": "k_merkle_lanes<%d, false>",
+                "rows": "k_merkle_rows<%d>", "coop": "k_merkle_coop<%d>", "fast": "k_merkle_level_fast<%d>",
+                "fast_ragged": "k_merkle_level_fast<%d>"}
+
+
+@pytest.mark.parametrize("arity", [1, 2, 3, 4])
+def test_merkle_level_every_form_edge_values(torch_cuda, hades_lib, oracle, arity):
+    """hades252_merkle_level_pad_dev in every level form (ragged levels of 4 097 .. 16 384 parents: the per-lane kernel),
+    edge-value children, tag p-1, an edge-value pad digest on ragged levels, guarded parents, vs the oracle."""
+    torch = torch_cuda
+    tag = P - 1
+    for form, sizes in LEVEL_SIZES.items():
+        if form == "fast_ragged" and arity == 1:
+            continue                                   # arity 1 is never ragged
+        for k, parents in enumerate(sizes):
+            ragged = arity > 1 and (form == "fast_ragged" or (k == 1 and form != "coop"))    # coop: full levels only
+            n_children = parents * arity - (1 if ragged else 0)
+            assert level_form(n_children, arity) == LEVEL_KERNEL[form] % arity, (form, parents)
+            ch = edge_scalars(n_children, 7 * n_children + arity)
+            padv = np.array(limbs_of(EDGE_VALUES[(parents + arity) % len(EDGE_VALUES)]), dtype=np.uint64)
+            dch, dpad = to_dev(torch, ch), to_dev(torch, padv)
+            exp = oracle.merkle_level_pad(ch, arity, tag, 1, padv).reshape(parents, 4)
+            got = guarded_call(torch, (parents, 4), lambda ptr: hades_lib.hades252_merkle_level_pad_dev(
+                dch.data_ptr(), n_children, ptr, arity, _tag(tag), 1, dpad.data_ptr(), None), (form, arity, n_children))
+            assert (to_host(got).reshape(parents, 4) == exp).all(), (form, arity, n_children)
+
+
+@pytest.mark.parametrize("arity,n_leaves", [(2, 1 << 15), (2, 1 << 16), (2, (1 << 15) + 5), (4, 4 ** 8), (4, 4 ** 8 * 2 + 3)])
+def test_merkle_tree_and_root_edge_values_guarded(torch_cuda, hades_lib, H, oracle, arity, n_leaves):
+    """Build (every level kept: tree != NULL) and root (ping-pong scratch of exactly hades252_merkle_scratch_bytes, a guard
+    after it) over edge-value leaves, at sizes where merkle_run fuses levels into k_merkle_coop (2^15 / 2^16 leaves of
+    arity 2) or runs a full coop level (4^8), and ragged ones with an edge-value padding table, vs the oracle."""
+    torch = torch_cuda
+    tag = P - 1
+    depth = H.merkle_depth(n_leaves, arity)
+    leaves = edge_scalars(n_leaves, n_leaves + arity)
+    dl = to_dev(torch, leaves)
+    ragged = arity ** depth != n_leaves
+    pad = edge_scalars(depth, 3 * depth, edge_ratio=1.0) if ragged else None
+    dpad = to_dev(torch, pad) if ragged else None
+    pptr = dpad.data_ptr() if ragged else None
+    levels = oracle.merkle_tree(leaves, arity, tag, 1, None if pad is None else pad.reshape(-1, 4))
+    n_nodes = sum(H.merkle_level_sizes(n_leaves, arity))
+    tree = guarded_call(torch, (n_nodes, 4), lambda ptr: hades_lib.hades252_merkle_build_pad_dev(
+        dl.data_ptr(), n_leaves, arity, _tag(tag), 1, pptr, ptr, None), "build")
+    assert (to_host(tree) == np.concatenate(levels)).all()
+    need = hades_lib.hades252_merkle_scratch_bytes(n_leaves, arity)
+    scr = Guarded(torch, (need // 8,))
+    root = guarded_call(torch, (4,), lambda ptr: hades_lib.hades252_merkle_root_pad_dev(
+        dl.data_ptr(), n_leaves, arity, scr.ptr, need, _tag(tag), 1, pptr, ptr, None), "root")
+    scr.check("root scratch", interior=False)         # fused levels leave part of the ping-pong buffers unused
+    assert (to_host(root) == levels[-1]).all()
+
+
+def _verify_tree(torch, hades_lib, H, oracle, arity, n_leaves, tag, seed):
+    """Edge-value leaves, their tree (guarded, checked against the oracle) and the device leaves."""
+    leaves = edge_scalars(n_leaves, seed)
+    dl = to_dev(torch, leaves).view(-1, 4)
+    n_nodes = sum(H.merkle_level_sizes(n_leaves, arity))
+    tree = guarded_call(torch, (n_nodes, 4), lambda ptr: hades_lib.hades252_merkle_build_pad_dev(
+        dl.data_ptr(), n_leaves, arity, _tag(tag), 1, None, ptr, None), "build")
+    assert (to_host(tree) == np.concatenate(oracle.merkle_tree(leaves, arity, tag, 1))).all()
+    return leaves, dl, tree
+
+
+@pytest.mark.parametrize("arity", [1, 2, 3, 4])
+def test_merkle_verify_every_form_edge_values(torch_cuda, hades_lib, H, oracle, arity):
+    """hades252_merkle_verify_dev at every size of every form: openings of edge-value leaves (guarded paths) verify back to
+    the root, into guarded roots; one tampered query per batch does not."""
+    torch = torch_cuda
+    tag = P - 1
+    nq_max = max(FORM_SIZES["fast"])
+    if arity == 1:
+        chain = edge_scalars(nq_max, 4242)
+        dc = to_dev(torch, chain).view(-1, 4)
+        cur = chain
+        for _ in range(3):
+            cur = oracle.merkle_level(cur, 1, tag, 1)
+        z = torch.zeros(nq_max, dtype=torch.int64, device="cuda")
+        for form, sizes in FORM_SIZES.items():
+            for m in sizes:
+                assert form_family(verify_form(m, 1)) == form_family(LEVEL_KERNEL[form])
+                got = guarded_call(torch, (m, 4), lambda ptr: hades_lib.hades252_merkle_verify_dev(
+                    dc.data_ptr(), z.data_ptr(), None, m, 3, 1, _tag(tag), 1, ptr, None), ("verify", m))
+                assert (to_host(got) == cur[:4 * m]).all(), m
+        return
+    n_leaves = arity ** 6 + 7
+    depth = H.merkle_depth(n_leaves, arity)
+    leaves, dl, tree = _verify_tree(torch, hades_lib, H, oracle, arity, n_leaves, tag, 99 + arity)
+    g = torch.Generator(device="cpu")
+    g.manual_seed(arity)
+    idx = torch.randint(0, n_leaves, (nq_max,), generator=g, dtype=torch.int64).cuda()
+    idx[0], idx[1] = n_leaves - 1, 0
+    paths = guarded_call(torch, (nq_max, depth, arity - 1, 4), lambda ptr: hades_lib.hades252_merkle_open_pad_dev(
+        dl.data_ptr(), tree.data_ptr(), n_leaves, arity, idx.data_ptr(), nq_max, None, ptr, None), "open")
+    lv = dl[idx].contiguous()
+    root = tree[-1]
+    for form, sizes in FORM_SIZES.items():
+        for m in sizes:
+            assert form_family(verify_form(m, arity)) == form_family(LEVEL_KERNEL[form])
+            p = paths[:m].clone()
+            t = m // 2
+            p[t, depth - 1, 0, 0] ^= 1
+            got = guarded_call(torch, (m, 4), lambda ptr: hades_lib.hades252_merkle_verify_dev(
+                lv.data_ptr(), idx.data_ptr(), p.data_ptr(), m, depth, arity, _tag(tag), 1, ptr, None), ("verify", m))
+            ok = (got == root.view(1, 4)).all(dim=1)
+            assert not bool(ok[t]) and int(ok.sum().item()) == m - 1, (form, m)
+    hp = to_host(paths[:2]).reshape(2, depth, arity - 1, 4)
+    for q in range(2):
+        i = int(idx[q].item())
+        assert (oracle.merkle_verify_path(leaves.reshape(-1, 4)[i], i, hp[q], arity, tag, 1) == to_host(root)).all()
+
+
+@pytest.mark.parametrize("arity,n_leaves", [(2, (1 << 17) + 3), (3, 3 ** 11), (4, 4 ** 9 + 3)])
+def test_merkle_update_every_form_edge_values(torch_cuda, hades_lib, H, oracle, arity, n_leaves):
+    """hades252_merkle_update_dev at every size of every form (level 1 has more parents than updates, so each runs its
+    update kernel there), edge-value new leaves, on a guarded tree: after each update the tree equals a fresh guarded
+    build, and after the last one the oracle's tree."""
+    torch = torch_cuda
+    tag = P - 1
+    depth = H.merkle_depth(n_leaves, arity)
+    assert H.merkle_level_sizes(n_leaves, arity)[0] > max(FORM_SIZES["fast"])
+    leaves = edge_scalars(n_leaves, n_leaves).reshape(-1, 4).copy()
+    dl = to_dev(torch, leaves.reshape(-1)).view(-1, 4)
+    n_nodes = sum(H.merkle_level_sizes(n_leaves, arity))
+    tree = Guarded(torch, (n_nodes, 4))
+    assert hades_lib.hades252_merkle_build_pad_dev(dl.data_ptr(), n_leaves, arity, _tag(tag), 1, None, tree.ptr, None) == 0
+    tree.check("build")
+    rng = random.Random(n_leaves)
+    for form, sizes in FORM_SIZES.items():
+        for nu in sizes:
+            assert form_family(update_form(nu, arity)) == form_family(LEVEL_KERNEL[form])
+            idx = [rng.randrange(n_leaves) for _ in range(nu)]
+            idx[0] = n_leaves - 1
+            fresh = edge_scalars(nu, nu * 7 + arity, edge_ratio=0.8).reshape(-1, 4)
+            leaves[idx] = fresh
+            dl.copy_(to_dev(torch, leaves.reshape(-1)).view(-1, 4))
+            didx = torch.tensor(idx, dtype=torch.int64, device="cuda")
+            assert hades_lib.hades252_merkle_update_dev(dl.data_ptr(), tree.ptr, n_leaves, arity, _tag(tag), 1, None,
+                                                        didx.data_ptr(), nu, None) == 0
+            tree.check(("update", form, nu))
+            ref = guarded_call(torch, (n_nodes, 4), lambda ptr: hades_lib.hades252_merkle_build_pad_dev(
+                dl.data_ptr(), n_leaves, arity, _tag(tag), 1, None, ptr, None), "rebuild")
+            assert torch.equal(tree.t, ref), (form, nu)
+    assert (to_host(tree.t) == np.concatenate(oracle.merkle_tree(leaves.reshape(-1), arity, tag, 1))).all()
