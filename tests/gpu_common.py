@@ -17,7 +17,7 @@ __all__ = ["KERNELS", "TAG", "TAG4", "CAP", "SITES_PERM", "to_dev", "to_host", "
            "kernel_available", "each_state_is_input_or_output", "_record", "word_boundary_values", "ARK_SHA256", "MDS_SHA256",
            "blob_bytes", "EDGE_VALUES", "edge_scalars", "SENTINEL", "Guarded", "guarded_call", "FORM_SIZES", "LEVEL_SIZES",
            "sponge_form", "absorb_form", "level_form", "verify_form", "update_form", "form_family", "oracle_sponge_var",
-           "SPONGE_BUCKETS", "COUNT_GRID_RECORDS"]
+           "SPONGE_BUCKETS", "COUNT_GRID_RECORDS", "CATALOGUE_LANES", "catalogue_states", "placed_batches"]
 
 KERNELS = [1, 2, 3, 4, 5]   # HADES252_KERNEL_LITERAL, _FAST (one state per lane), _COOP (five waves per state), _LANES (one
                             # state per wave, elements spread over 16-lane rows), _ROWS (one state per row, four per wave)
@@ -246,3 +246,30 @@ def oracle_sponge_var(oracle, pool, offsets, lengths, cap, pad, threads=16):
         parts = list(ex.map(lambda a: oracle.sponge_var(pool, offsets[a:a + step], lengths[a:a + step], cap, pad),
                             range(0, n, step)))
     return np.concatenate(parts)
+
+
+# ---------------------------------------------------------------------------------------------
+# edge values inside the rounds: the catalogue of tests/round_inverse.py as device input, and batches that place it at the
+# lanes where a kernel's wave, row and block boundaries fall
+# ---------------------------------------------------------------------------------------------
+CATALOGUE_LANES = (0, 63, 64, 255, 256)          # ... and the last lane of the batch
+
+
+def catalogue_states():
+    """(states, labels): the round_inverse catalogue as in-memory Montgomery limbs, uint64 [entries, 20]."""
+    import round_inverse as RI
+    cat = RI.edge_catalogue()
+    states = np.array([[l for v in inp for l in limbs_of(S.to_mont(v))] for inp, _ in cat], dtype=np.uint64)
+    return states, [lab for _, lab in cat]
+
+
+def placed_batches(states, n, fill):
+    """Batches of n states that together hold every row of `states` (uint64 [entries, 20]) once: the rows sit at lanes
+    CATALOGUE_LANES and n - 1 (those below n), the rest of each batch is `fill` (uint64 [n, 20]).  Yields (batch
+    [n, 20], lanes, row indices)."""
+    lanes = sorted({l for l in CATALOGUE_LANES if l < n} | {n - 1})
+    for first in range(0, len(states), len(lanes)):
+        idx = list(range(first, min(first + len(lanes), len(states))))
+        b = fill.copy()
+        b[lanes[:len(idx)]] = states[idx]
+        yield b, lanes[:len(idx)], idx

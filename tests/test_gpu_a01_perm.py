@@ -472,3 +472,52 @@ def test_multi_launch_loop_with_lowered_cap(torch_cuda, hades_lib):
     env = dict(os.environ, HADES252_TEST_MAX_LAUNCH="4096")
     r = subprocess.run([sys.executable, "-c", _MULTI_LAUNCH_CHILD], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "MULTI_LAUNCH_OK" in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]
+
+
+# ---------------------------------------------------------------------------------------------
+# edge values INSIDE the rounds (tests/round_inverse.py; which entry reaches which routine: tests/test_round_inverse.py).
+# The outputs 0 reach finalize with x >= 0 (both conditional subtractions, and exactly p through fr_cond_sub_p) in the fast,
+# coop, lanes and rows kernels; the literal kernel's round keys meet w + c = p at every zero S-box input.
+# ---------------------------------------------------------------------------------------------
+def _perm_guarded(torch, H, kernel, batch):
+    g = Guarded(torch, batch.shape, init=to_dev(torch, batch).view(batch.shape))
+    H.ScalarStrategy(kernel).perm(g.t.view(-1))
+    return to_host(g.check("kernel %d, n %d" % (kernel, batch.shape[0]))).reshape(-1, 20)
+
+
+def _check_placed(torch, H, oracle, kernel, n, states, labels, exp):
+    fill = oracle.gen_b(977 * n, 5 * n).reshape(n, 20)
+    exp_fill = oracle.perm_batch(fill).reshape(n, 20)
+    for batch, lanes, idx in placed_batches(states, n, fill):
+        got = _perm_guarded(torch, H, kernel, batch)
+        want = exp_fill.copy()
+        want[lanes] = exp[idx]
+        bad = [int(i) for i in np.nonzero((got != want).any(axis=1))[0]]
+        assert not bad, "kernel %d, n %d: lanes %s wrong (%s)" % (
+            kernel, n, bad[:6], [str(labels[idx[lanes.index(i)]]) for i in bad if i in lanes][:4])
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_catalogue_through_each_selector(torch_cuda, hades_lib, H, oracle, kernel):
+    """The whole catalogue through each forced kernel: packed (one entry per lane, guarded) and placed at lanes 0, 63, 64,
+    255, 256 and the last lane of 300-state batches of random states; every state bit for bit against the oracle."""
+    torch = torch_cuda
+    if not kernel_available(hades_lib, torch, kernel):
+        pytest.skip("kernel %d not built" % kernel)
+    states, labels = catalogue_states()
+    exp = oracle.perm_batch(states).reshape(-1, 20)
+    got = _perm_guarded(torch, H, kernel, states)
+    bad = [str(labels[i]) for i in np.nonzero((got != exp).any(axis=1))[0]]
+    assert not bad, "kernel %d: %d entries wrong, first %s" % (kernel, len(bad), bad[:6])
+    _check_placed(torch, H, oracle, kernel, 300, states, labels, exp)
+
+
+@pytest.mark.parametrize("form", sorted(FORM_SIZES))
+def test_catalogue_through_the_default_dispatch_at_every_form_size(torch_cuda, H, oracle, form):
+    """The default dispatch at every size of FORM_SIZES: the catalogue spread over as many batches as it takes, at lanes 0,
+    63, 64, 255, 256 and the last lane (those the size has), so that every entry runs in every form."""
+    torch = torch_cuda
+    states, labels = catalogue_states()
+    exp = oracle.perm_batch(states).reshape(-1, 20)
+    for n in FORM_SIZES[form]:
+        _check_placed(torch, H, oracle, 0, n, states, labels, exp)

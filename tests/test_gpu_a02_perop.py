@@ -18,6 +18,7 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import hades_spec as S  # noqa: E402,F401
 from oracle_lib import P, R, limbs_of, int_of, digest_ref  # noqa: E402,F401
 from gpu_common import *  # noqa: E402,F401,F403  (helpers shared by the GPU tier; fixtures torch_cuda / H: conftest.py)
+import round_inverse as RI  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -178,3 +179,73 @@ def test_perm_trace_fast_2pow16_digest(torch_cuda, H):
     out = st.clone()
     H.ScalarStrategy().perm(out)
     assert torch.equal(fast[66].reshape(-1), out.reshape(-1))
+
+
+# ---------------------------------------------------------------------------------------------
+# edge values INSIDE the rounds (tests/round_inverse.py; which entry reaches which routine: tests/test_round_inverse.py):
+# each per-op entry point gets the state its stage of the entry's round holds -- the round key meets w + c = p at every zero
+# "sbox_in" entry, the S-box kernel an input of 0 / +-1, the matrix an "mds_in" state with a held or an r1 zero, the fused
+# rounds the state before them -- and both traces run over the whole catalogue into guarded buffers
+# ---------------------------------------------------------------------------------------------
+def test_per_op_kernels_on_catalogue_rounds(torch_cuda, H, hades_lib, oracle):
+    """For the entries of each round r, from the oracle's trace[r - 1]: add_round_key (cursor and round forms), the S-box
+    on the keyed words, mul_matrix on the "mds_in" states, apply_full_round and apply_partial_round (cursor and round
+    forms), each against the oracle's per-op functions."""
+    torch = torch_cuda
+    states, labels = catalogue_states()
+    strat = H.ScalarStrategy()
+    by_round = {}
+    for i, lab in enumerate(labels):
+        by_round.setdefault(lab.r, []).append(i)
+    for r, idx in sorted(by_round.items()):
+        prev = np.array([states[i] if r == 0 else oracle.perm_trace(states[i])[1][r - 1].reshape(-1) for i in idx],
+                        dtype=np.uint64).reshape(-1)
+        n = len(idx)
+        ark = oracle.add_round_key(prev, r)
+        for call in (lambda b: strat.add_round_key(H.RoundConstantsIter(5 * r), b) or 0,
+                     lambda b: hades_lib.hades252_add_round_key_dev(b.data_ptr(), n, r, None)):
+            buf = to_dev(torch, prev)
+            assert call(buf) == 0
+            torch.cuda.synchronize()
+            assert (to_host(buf) == ark).all(), r
+        buf = to_dev(torch, ark)
+        strat.quintic_s_box(buf)
+        assert (to_host(buf) == oracle.quintic_s_box(ark)).all(), r
+        mds_in = oracle.quintic_s_box(ark) if RI.is_full(r) else _partial_sbox(oracle, ark)
+        buf = to_dev(torch, mds_in)
+        strat.mul_matrix(H.RoundConstantsIter(), buf)
+        assert (to_host(buf) == oracle.mul_matrix(mds_in)).all(), r
+        for full, exp in ((True, oracle.full_round(prev, r)), (False, oracle.partial_round(prev, r))):
+            at = strat.apply_full_round if full else strat.apply_partial_round
+            plain = hades_lib.hades252_apply_full_round_dev if full else hades_lib.hades252_apply_partial_round_dev
+            buf = to_dev(torch, prev)
+            at(H.RoundConstantsIter(5 * r), buf)
+            assert (to_host(buf) == exp).all(), (r, full)
+            buf = to_dev(torch, prev)
+            assert plain(buf.data_ptr(), n, r, None) == 0
+            torch.cuda.synchronize()
+            assert (to_host(buf) == exp).all(), (r, full)
+
+
+def _partial_sbox(oracle, ark):
+    """the "mds_in" states of a partial round: the S-box on word 4 of the keyed states"""
+    st = ark.reshape(-1, 5, 4).copy()
+    st[:, 4, :] = oracle.quintic_s_box(st[:, 4, :].copy()).reshape(-1, 4)
+    return st.reshape(-1)
+
+
+@pytest.mark.parametrize("kernel", [1, 2], ids=["literal", "fast"])
+def test_perm_trace_on_the_catalogue_guarded(torch_cuda, H, oracle, kernel):
+    """The literal and the true-form per-round trace of the whole catalogue, guarded: every round of every record against
+    the oracle's trace."""
+    torch = torch_cuda
+    states, labels = catalogue_states()
+    n = len(states)
+    g = Guarded(torch, (67, n, 5, 4))
+    dev = to_dev(torch, states.reshape(-1))
+    H.perm_trace(dev, kernel=kernel, out=g.t)
+    host = to_host(g.check("trace, kernel %d" % kernel)).reshape(67, n, 20)
+    assert (to_host(dev) == states.reshape(-1)).all()
+    for i in range(n):
+        _, otr = oracle.perm_trace(states[i])
+        assert (host[:, i, :] == otr.reshape(67, 20)).all(), str(labels[i])

@@ -281,3 +281,64 @@ def test_finalize_window_both_rare_sides_on_the_device(torch_cuda, H):
         assert int_of(row) == x % P, hex(x)
     with pytest.raises(Exception):
         H.fr_op(H.FR_REDUCE_SIGNED, a, impl=H.FR_IMPL_SATURATED32)              # a radix-2^29 routine only
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# edge values INSIDE the rounds (tests/round_inverse.py; which entry reaches which routine: tests/test_round_inverse.py):
+# every zero wire -- a zero trace word ("zero" at "out"), a zero S-box input and its v2, v4, v5 ("sbox_edge"), a zero r1
+# row ("r1_zero") -- sends exactly p through finalize32's conditional subtraction; the scaled trace's exit
+# (finalize_window) takes its rare x >= 0 side where the held value is exactly 0 (the all-zero output, round 0's all-zero
+# S-box input, the held zeros r5/out/w1, r33/out/w1 and w3), and stores 0 at every held zero
+# ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [257, 4097])
+def test_witness_on_the_catalogue_every_wire_guarded(torch_cuda, H, n):
+    """perm_witness on the catalogue padded with random states to a ragged n (spread over batches where n is smaller), in a
+    guarded wire buffer: all 972 wires of every catalogue record against perm_gadget."""
+    import round_inverse as RI
+    torch = torch_cuda
+    cat = RI.edge_catalogue()
+    states, labels = catalogue_states()
+    fill = to_host(H.gen_b(5 * n, "cuda", first_elem=5 * 4242)).reshape(n, 20)
+    for first in range(0, len(states), n):
+        idx = list(range(first, min(first + n, len(states))))
+        batch = fill.copy()
+        batch[:len(idx)] = states[idx]
+        g = Guarded(torch, (972, n, 4))
+        H.perm_witness(to_dev(torch, batch.reshape(-1)), out=g.t)
+        host = to_host(g.check("witness, n %d" % n)).reshape(972, n, 4)
+        for k, i in enumerate(idx):
+            spec = []
+            S.perm_gadget(cat[i][0], spec)
+            got = [int_of(host[w, k]) for w in range(972)]
+            bad = [w for w in range(972) if got[w] != S.to_mont(spec[w])]
+            assert not bad, (str(labels[i]), bad[:8])
+
+
+def test_scaled_trace_on_the_catalogue_guarded(torch_cuda, H, oracle):
+    """The scaled trace of the whole catalogue into a guarded buffer, un-scaled on the host with trace_scale_table: every
+    round of every record against the oracle's trace; every held zero stored as exactly 0."""
+    import round_inverse as RI
+    torch = torch_cuda
+    states, labels = catalogue_states()
+    n = len(states)
+    trace_d, _ = RI.held_offsets()
+    mul, add = H.trace_scale_table()
+    mul = [int_of(m) for m in mul]
+    add = [[int_of(a) for a in row] for row in add]
+    r_inv = pow(R, -1, P)
+    g = Guarded(torch, (67, n, 5, 4))
+    H.perm_trace_scaled(to_dev(torch, states.reshape(-1)), out=g.t)
+    host = to_host(g.check("scaled trace")).reshape(67, n, 5, 4)
+    held_zeros = 0
+    for i, lab in enumerate(labels):
+        _, otr = oracle.perm_trace(states[i])
+        for r in range(67):
+            for w in range(5):
+                scaled = int_of(host[r, i, w])
+                assert scaled < P and (scaled * mul[r] % P * r_inv + add[r][w]) % P == int_of(otr[r][w]), (str(lab), r, w)
+        if lab.stage == "out":
+            for w, v in zip(lab.words, lab.values):
+                if v == trace_d[lab.r][w]:
+                    assert int_of(host[lab.r, i, w]) == 0, (str(lab), w)
+                    held_zeros += 1
+    assert held_zeros >= 60, held_zeros                                  # 65: the true zeros of the full rounds included
