@@ -26,6 +26,9 @@ KERNEL_LANES = 4
 KERNEL_ROWS = 5
 MULTI_VIRTUAL = 1
 CIPHER_MAX_LEN = 1024
+SAFE_MAX_CALLS = 64
+SAFE_MAX_WORDS = 1 << 20
+SAFE_ABSORB = 1 << 31
 
 # every symbol include/hades252.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -137,6 +140,13 @@ SIGNATURES = {
                                                     c_void_p, c_void_p, c_void_p, c_void_p]),
     "hades252_cipher_decrypt_witness_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, POINTER(c_uint64),
                                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hades252_safe_pattern": (c_int, [POINTER(ctypes.c_uint32), c_size_t, POINTER(c_size_t), POINTER(c_size_t),
+                                      POINTER(c_size_t)]),
+    "hades252_safe_hash_dev": (c_int, [c_void_p, c_size_t, POINTER(ctypes.c_uint32), c_size_t, POINTER(c_uint64), c_void_p,
+                                       c_void_p]),
+    "hades252_safe_absorb_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, POINTER(ctypes.c_uint32), c_void_p]),
+    "hades252_safe_squeeze_dev": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, POINTER(ctypes.c_uint32), c_void_p]),
+    "hades252_safe_hash": (c_int, [c_void_p, c_size_t, POINTER(ctypes.c_uint32), c_size_t, POINTER(c_uint64), c_void_p]),
     "hades252_gen_b_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_uint64, c_void_p]),
     "hades252_gen_a_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_void_p]),
     "hades252_digest_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_void_p, c_void_p]),

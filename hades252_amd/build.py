@@ -29,13 +29,13 @@ DEVICE_DEPS = ["fr32.hpp", "staging.hpp", "hades_literal.hpp", "hades_fast.hpp",
 # host code that decides WHAT is launched and with which geometry / LDS / level-fusion policy: a kernel's traffic per launch
 # and the launches that make a tree depend on it
 LAUNCH_POLICY_DEPS = ["launch.hpp", "abi_perm.hpp", "abi_merkle.hpp", "abi_sponge.hpp"]
-# kernels (and their launchers) that no committed counter record covers: the batched cipher, the chain witnesses.  They are rebuilt like every
+# kernels (and their launchers) that no committed counter record covers: the batched cipher, the duplex sponge, the chain witnesses.  They are rebuilt like every
 # other source (DEPS) but stay out of device_source_hash: they neither define nor launch any kernel of the
 # `secondary_kernels` record, so an edit of them cannot change that record's traffic and must not drop it from bench.py.
 # A kernel that gets a counter record of its own moves to DEVICE_DEPS / LAUNCH_POLICY_DEPS with it.
-UNRECORDED_KERNEL_DEPS = ["kernels_cipher.hpp", "abi_cipher.hpp", "kernels_witness.hpp", "abi_witness.hpp"]
+UNRECORDED_KERNEL_DEPS = ["kernels_cipher.hpp", "abi_cipher.hpp", "kernels_safe.hpp", "abi_safe.hpp", "kernels_witness.hpp", "abi_witness.hpp"]
 # host plumbing (error / fault hook, page-locked memory, pipe pool, chunk pipeline, one-shot host callers, generators)
-HOST_DEPS = ["hades252.hip", "host_fault.hpp", "abi_util.hpp", "host_pin.hpp", "host_pool.hpp", "host_pipe.hpp", "host_callers.hpp", "host_cipher.hpp"]
+HOST_DEPS = ["hades252.hip", "host_fault.hpp", "abi_util.hpp", "host_pin.hpp", "host_pool.hpp", "host_pipe.hpp", "host_callers.hpp", "host_cipher.hpp", "host_safe.hpp"]
 DEPS = HOST_DEPS + LAUNCH_POLICY_DEPS + DEVICE_DEPS + UNRECORDED_KERNEL_DEPS + [os.path.join("..", "..", "include", "hades252.h")]
 # what the dominant kernel (k_perm_fast) is made of: profiles recorded for it stay valid while these are unchanged
 PERM_FAST_DEPS = ["fr32.hpp", "staging.hpp", "hades_fast.hpp", "k_perm_fast.hpp"]

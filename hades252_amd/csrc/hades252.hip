@@ -32,6 +32,7 @@ using namespace hades;
 #include "kernels_merkle.hpp"
 #include "kernels_sponge.hpp"
 #include "kernels_cipher.hpp"
+#include "kernels_safe.hpp"
 #include "kernels_witness.hpp"
 #include "kernels_aux.hpp"
 
@@ -45,10 +46,12 @@ using namespace hades;
 #include "abi_merkle.hpp"
 #include "abi_sponge.hpp"
 #include "abi_cipher.hpp"
+#include "abi_safe.hpp"
 #include "abi_witness.hpp"
 #include "abi_util.hpp"
 #include "host_pin.hpp"
 #include "host_pool.hpp"
 #include "host_pipe.hpp"
 #include "host_callers.hpp"
+#include "host_safe.hpp"
 #include "host_cipher.hpp"

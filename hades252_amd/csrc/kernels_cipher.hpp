@@ -47,18 +47,20 @@ __device__ __forceinline__ bool fr_eq(const Fr &a, const Fr &b) {
 // wave's 64 messages move through the wave's LDS slab: 8 lanes carry the (up to) 128 contiguous bytes of one message,
 // 8 messages per instruction -- no lane walks HBM with a message-sized stride.  The slab is wave-private and a wave's LDS
 // operations execute in order: compiler fences only (as in k_sponge).
+// `lo` (0 for the cipher) shifts the slots: the words land in w[lo .. lo + cnt), the other slots read zero (the duplex
+// sponge of kernels_safe.hpp resumes a block at position lo).
 __device__ __forceinline__ void cipher_gather(const uint8_t *base, size_t stride, size_t first, int cnt, size_t rec0, size_t n,
-                                              uint8_t *slab, Fr (&w)[4]) {
+                                              uint8_t *slab, Fr (&w)[4], int lo = 0) {
     constexpr int kRec = lds_rec_bytes(4);
     const int lane = threadIdx.x & (kWave - 1), part = lane & 7, j = part >> 1;
     // message 8k + lane / 8: one per-lane address, a wave-uniform step of 8 messages
-    const uint8_t *p = base + ((rec0 + (lane >> 3)) * stride + first + j) * 32 + (part & 1) * 16;
+    const uint8_t *p = base + ((rec0 + (lane >> 3)) * stride + first + j - lo) * 32 + (part & 1) * 16;
     const size_t step = 8 * stride * 32;
 #pragma unroll
     for (int k = 0; k < 8; k++) {
         const int m = 8 * k + (lane >> 3);
         uint4 v = make_uint4(0, 0, 0, 0);
-        if (j < cnt && rec0 + m < n) v = *reinterpret_cast<const uint4 *>(p + k * step);
+        if (j >= lo && j < lo + cnt && rec0 + m < n) v = *reinterpret_cast<const uint4 *>(p + k * step);
         *reinterpret_cast<uint4 *>(slab + m * kRec + part * 16) = v;
     }
     wave_lds_fence();
@@ -72,12 +74,12 @@ __device__ __forceinline__ void cipher_gather(const uint8_t *base, size_t stride
     wave_lds_fence();
 }
 
-// The reverse: w[0..cnt) of every lane -> words [first, first + cnt) of its message.  With ZERO_BAD, zeros go to the
+// The reverse: w[lo .. lo + cnt) of every lane -> words [first, first + cnt) of its message.  With ZERO_BAD, zeros go to the
 // messages whose owner lane has bad set, nothing to the others (the lane that stores a given address is the same in
 // both forms, so a zeroing pass is ordered after the earlier store by program order).
 template <bool ZERO_BAD>
 __device__ __forceinline__ void cipher_scatter(uint8_t *base, size_t stride, size_t first, int cnt, size_t rec0, size_t n,
-                                               uint8_t *slab, const Fr (&w)[4], bool bad = false) {
+                                               uint8_t *slab, const Fr (&w)[4], bool bad = false, int lo = 0) {
     constexpr int kRec = lds_rec_bytes(4);
     const int lane = threadIdx.x & (kWave - 1), part = lane & 7, j = part >> 1;
     if constexpr (!ZERO_BAD) {
@@ -86,7 +88,7 @@ __device__ __forceinline__ void cipher_scatter(uint8_t *base, size_t stride, siz
         wave_lds_fence();
     }
     const uint64_t bad_mask = ZERO_BAD ? __ballot(bad) : 0;
-    uint8_t *p = base + ((rec0 + (lane >> 3)) * stride + first + j) * 32 + (part & 1) * 16;
+    uint8_t *p = base + ((rec0 + (lane >> 3)) * stride + first + j - lo) * 32 + (part & 1) * 16;
     const size_t step = 8 * stride * 32;
 #pragma unroll
     for (int k = 0; k < 8; k++) {
@@ -94,7 +96,7 @@ __device__ __forceinline__ void cipher_scatter(uint8_t *base, size_t stride, siz
         uint4 v = make_uint4(0, 0, 0, 0);
         if constexpr (!ZERO_BAD) v = *reinterpret_cast<const uint4 *>(slab + m * kRec + part * 16);
         const bool go = ZERO_BAD ? ((bad_mask >> m) & 1) != 0 : true;
-        if (go && j < cnt && rec0 + m < n) *reinterpret_cast<uint4 *>(p + k * step) = v;
+        if (go && j >= lo && j < lo + cnt && rec0 + m < n) *reinterpret_cast<uint4 *>(p + k * step) = v;
     }
     if constexpr (!ZERO_BAD) wave_lds_fence();
 }

@@ -939,6 +939,144 @@ def cipher_decrypt_host(ciphers: np.ndarray, keys: np.ndarray, nonces: np.ndarra
     return out, ok, int(rej.value)
 
 
+# ---- batched duplex sponge (include/hades252.h, CONVENTION UNPINNED) ---------------------------------------------------
+_SAFE_KINDS = {"absorb": _lib.SAFE_ABSORB, "squeeze": 0}
+
+
+def _safe_calls(pattern, what: str):
+    """[("absorb", 3), ("squeeze", 2)] -> (ctypes uint32 array, count); the library judges validity."""
+    words = []
+    for call in pattern:
+        kind, n = call
+        if kind not in _SAFE_KINDS or not isinstance(n, int) or not 0 <= n < _lib.SAFE_ABSORB:
+            raise ValueError("%s: a call is (\"absorb\" | \"squeeze\", length), got %r" % (what, (call,)))
+        words.append(_SAFE_KINDS[kind] | n)
+    return (ctypes.c_uint32 * max(len(words), 1))(*words), len(words)
+
+
+def safe_pattern(calls):
+    """Validate an IO pattern (``hades252_safe_pattern``; no device needed) -> (words absorbed, words squeezed, permutations)
+    per sponge.  Raises ValueError for an invalid pattern."""
+    arr, k = _safe_calls(calls, "safe_pattern")
+    n_in, n_out, n_perms = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    if _lib.lib().hades252_safe_pattern(arr, k, ctypes.byref(n_in), ctypes.byref(n_out), ctypes.byref(n_perms)) != _lib.OK:
+        raise ValueError("safe_pattern: %r is not a valid IO pattern (absorb first, squeeze last, no empty call, at most %d "
+                         "calls and %d words each way)" % (list(calls), _lib.SAFE_MAX_CALLS, _lib.SAFE_MAX_WORDS))
+    return int(n_in.value), int(n_out.value), int(n_perms.value)
+
+
+def safe_tag_input(pattern, domain_sep: int) -> bytes:
+    """The bytes SAFE hashes into a tag: the aggregated calls as big-endian 32-bit words, then the 64-bit domain separator
+    big-endian.  NAMED, NOT PINNED (like SPONGE_PRESETS); hashing them to a scalar stays the caller's."""
+    safe_pattern(pattern)
+    words = []
+    for kind, n in pattern:
+        if words and (words[-1] & _lib.SAFE_ABSORB) == _SAFE_KINDS[kind]:
+            words[-1] += n
+        else:
+            words.append(_SAFE_KINDS[kind] | n)
+    return b"".join(w.to_bytes(4, "big") for w in words) + int(domain_sep).to_bytes(8, "big")
+
+
+def safe_hash(inputs_t, pattern, tag_mont: int):
+    """Batched duplex sponge, the whole pattern in one launch (``hades252_safe_hash_dev``): inputs_t holds n x n_in scalars
+    (CUDA tensor, Montgomery limbs, message-major, in call order).  Returns [n, n_out, 4] int64."""
+    import torch
+    n_in, n_out, _ = safe_pattern(pattern)
+    arr, k = _safe_calls(pattern, "safe_hash")
+    ptr, n_words, dev = _dev_buffer(inputs_t, 32, "safe_hash")
+    if n_words % n_in:
+        raise ValueError("safe_hash: %d scalars are not a whole number of inputs of %d" % (n_words, n_in))
+    n = n_words // n_in
+    out = torch.empty((n, n_out, 4), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().hades252_safe_hash_dev(ptr, n, arr, k, _tag_arr(tag_mont), out.data_ptr(), _stream_ptr(dev)),
+              "safe_hash")
+    return out
+
+
+def safe_hash_host(inputs: np.ndarray, pattern, tag_mont: int) -> np.ndarray:
+    """``hades252_safe_hash`` on a HOST array (C-contiguous uint64, Montgomery limbs): -> [n, n_out, 4] uint64."""
+    n_in, n_out, _ = safe_pattern(pattern)
+    arr, k = _safe_calls(pattern, "safe_hash_host")
+    n_words = _host_scalars(inputs, "safe_hash_host")
+    if n_words % n_in:
+        raise ValueError("safe_hash_host: %d scalars are not a whole number of inputs of %d" % (n_words, n_in))
+    n = n_words // n_in
+    out = np.zeros((n, n_out, 4), dtype=np.uint64)
+    check(_lib.lib().hades252_safe_hash(_ptr(inputs), n, arr, k, _tag_arr(tag_mont), _ptr(out)), "safe_hash_host")
+    return out
+
+
+class SafeSponge:
+    """n duplex sponges resident on the device that follow one IO pattern call by call (``hades252_safe_absorb_dev`` /
+    ``_squeeze_dev``), for callers whose next input depends on what they read.  Calls may be split (absorb(2) then
+    absorb(1) serves ("absorb", 3)); a call of the wrong kind, one that overruns the pattern's current call, or ``finish``
+    before the pattern is used up raises ValueError: the analogue of dusk-safe's IO-pattern violation."""
+
+    def __init__(self, n: int, pattern, tag_mont: int, device="cuda"):
+        import torch
+        safe_pattern(pattern)
+        self._todo = []                                   # aggregated calls still to serve: [kind, words left]
+        for kind, k in pattern:
+            if self._todo and self._todo[-1][0] == kind:
+                self._todo[-1][1] += k
+            else:
+                self._todo.append([kind, k])
+        self._cursor = ctypes.c_uint32(0)
+        self.states = torch.empty((n, WIDTH, 4), dtype=torch.int64, device=device)
+        with torch.cuda.device(self.states.device):
+            check(_lib.lib().hades252_sponge_init_dev(self.states.data_ptr(), n, _tag_arr(tag_mont),
+                                                      _stream_ptr(self.states.device)), "SafeSponge")
+
+    def _take(self, kind: str, k: int) -> None:
+        if k <= 0:
+            raise ValueError("SafeSponge.%s: a call moves at least one word" % kind)
+        if not self._todo:
+            raise ValueError("SafeSponge.%s: the IO pattern is used up" % kind)
+        if self._todo[0][0] != kind:
+            raise ValueError("SafeSponge.%s: the IO pattern expects %s(%d) here" % (kind, self._todo[0][0], self._todo[0][1]))
+        if k > self._todo[0][1]:
+            raise ValueError("SafeSponge.%s: %d words, the IO pattern has %d left in this call" % (kind, k, self._todo[0][1]))
+
+    def _took(self, k: int) -> None:
+        self._todo[0][1] -= k
+        if self._todo[0][1] == 0:
+            self._todo.pop(0)
+
+    def absorb(self, t) -> None:
+        """t: n x k scalars (state-major) for the next k words of the current absorb call."""
+        import torch
+        n = self.states.shape[0]
+        ptr, n_words, dev = _dev_buffer(t, 32, "SafeSponge.absorb")
+        _same_device("SafeSponge.absorb", self.states.device, dev)
+        if n == 0 or n_words % n:
+            raise ValueError("SafeSponge.absorb: %d scalars do not split evenly over %d sponges" % (n_words, n))
+        k = n_words // n
+        self._take("absorb", k)
+        with torch.cuda.device(dev):
+            check(_lib.lib().hades252_safe_absorb_dev(self.states.data_ptr(), n, ptr, k, ctypes.byref(self._cursor),
+                                                      _stream_ptr(dev)), "SafeSponge.absorb")
+        self._took(k)
+
+    def squeeze(self, k: int):
+        """-> [n, k, 4] int64: the next k words of the current squeeze call."""
+        import torch
+        n, dev = self.states.shape[0], self.states.device
+        self._take("squeeze", k)
+        out = torch.empty((n, k, 4), dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            check(_lib.lib().hades252_safe_squeeze_dev(self.states.data_ptr(), n, k, out.data_ptr(),
+                                                       ctypes.byref(self._cursor), _stream_ptr(dev)), "SafeSponge.squeeze")
+        self._took(k)
+        return out
+
+    def finish(self) -> None:
+        """The pattern must be used up (dusk-safe's `finish`)."""
+        if self._todo:
+            raise ValueError("SafeSponge.finish: the IO pattern still expects %s(%d)" % tuple(self._todo[0]))
+
+
 GEN_SEED = 0x4861646573323532
 
 

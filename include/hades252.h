@@ -478,6 +478,51 @@ int hades252_cipher_encrypt(const uint64_t *msgs, const uint64_t *keys, const ui
 int hades252_cipher_decrypt(const uint64_t *ciphers, const uint64_t *keys, const uint64_t *nonces, size_t n_msgs,
                             size_t msg_len, const uint64_t domain_mont[4], uint64_t *msgs, uint8_t *ok, size_t *n_rejected);
 
+/* ---- batched duplex sponge (the SAFE sponge of dusk-safe, which dusk-poseidon's hash, Merkle level and cipher use after
+ * 0.33) ---- CONVENTION UNPINNED
+ * n_msgs independent sponges that all follow one IO pattern: a list of absorb and squeeze calls fixed in advance, freely
+ * interleaved, no padding.  Neither crate is part of the reference tree: the construction is recalled from dusk-safe /
+ * dusk-poseidon and pinned only to this repository's model (tests/safe_model.py); how a tag is derived and which domain
+ * separator a caller uses is theirs, so the tag is a parameter.  Rate 4, width 5, per sponge:
+ *   state = [tag, 0, 0, 0, 0]; pos_absorb = 0; pos_squeeze = 0
+ *   absorb(x_0 .. x_{n-1}):  for each x:  if pos_absorb == 4: state = perm(state); pos_absorb = 0
+ *                                         state[1 + pos_absorb] += x;  pos_absorb += 1
+ *                            afterwards:  pos_squeeze = 4                     (the next squeeze permutes first)
+ *   squeeze(n):              n times:     if pos_squeeze == 4: state = perm(state); pos_squeeze = 0; pos_absorb = 0
+ *                                         output state[1 + pos_squeeze];  pos_squeeze += 1
+ * A call is one uint32_t: HADES252_SAFE_ABSORB (bit 31) set = absorb, the low 31 bits = its length (SAFE's own encoding).
+ * A pattern is valid when it is not empty, starts with an absorb, ends with a squeeze, has no call of length 0, at most
+ * HADES252_SAFE_MAX_CALLS calls and at most HADES252_SAFE_MAX_WORDS words in and as many out per sponge.  Consecutive
+ * calls of one kind behave exactly like one call of the summed length.  Instances: [absorb(L), squeeze(1)] with tag c is
+ * hades252_sponge_hash_dev(.., capacity c, pad_mode 0) in ceil(L / 4) permutations; [absorb(4), squeeze(1)] with tag 15 is
+ * the arity-4 Merkle level; the crate's cipher is [absorb(2), absorb(1), squeeze(M), absorb(M), squeeze(1)] with cipher =
+ * message + squeezed words, composed by the caller over the streaming calls below.
+ * Layouts (AoS, 32 B per scalar, Montgomery limbs, canonical -- not checked, as for perm): d_in n_msgs x n_in words in call
+ * order, d_out n_msgs x n_out words in call order, both message-major.
+ * hades252_safe_pattern validates a pattern without touching a device and returns the words absorbed and squeezed per
+ * sponge and the permutations per sponge (each pointer may be NULL).  hades252_safe_hash_dev runs the whole pattern in one
+ * launch, asynchronous on `stream` (the pattern travels in the kernel arguments).  Up to 1 024 sponges run one per wave
+ * (latency), more run one per lane; there is no four-per-wave or five-waves form: 1 025 .. 16 384 sponges run per lane.
+ * Streaming, for callers whose next input depends on what they read: states are those of hades252_sponge_init_dev
+ * (capacity = tag, 160 B each); the two positions live in a caller-owned *cursor (0 = fresh; opaque otherwise), one for
+ * the whole batch.  The streaming calls do not know a pattern: any sequence is served, and any split of a pattern into
+ * streaming calls gives the bytes of the one-shot call.  len is 1 .. HADES252_SAFE_MAX_WORDS.
+ * Rules: n_msgs / n_states = 0 is a no-op success (the cursor stays); a NULL array, a scalar array that is not 16-byte
+ * aligned, an invalid pattern, length or cursor value, or more than 2^30 sponges is HADES252_ERR_INVALID_ARG, all decided
+ * before the device is touched; *cursor is written on success only. */
+#define HADES252_SAFE_MAX_CALLS 64
+#define HADES252_SAFE_MAX_WORDS 1048576
+#define HADES252_SAFE_ABSORB 2147483648u
+int hades252_safe_pattern(const uint32_t *calls, size_t n_calls, size_t *n_in, size_t *n_out, size_t *n_perms);
+int hades252_safe_hash_dev(const void *d_in, size_t n_msgs, const uint32_t *calls, size_t n_calls, const uint64_t tag_mont[4],
+                           void *d_out, void *stream);
+int hades252_safe_absorb_dev(void *d_states, size_t n_states, const void *d_in, size_t len, uint32_t *cursor, void *stream);
+int hades252_safe_squeeze_dev(void *d_states, size_t n_states, size_t len, void *d_out, uint32_t *cursor, void *stream);
+/* The same on host memory (any n_msgs: chunked through a pooled pipe, device memory bounded; ordinary or page-locked
+ * memory). */
+int hades252_safe_hash(const uint64_t *in, size_t n_msgs, const uint32_t *calls, size_t n_calls, const uint64_t tag_mont[4],
+                       uint64_t *out);
+
 /* ---- gadget witnesses of the cipher (f5): the third chain of row f4 ---- CONVENTION UNPINNED
  * The construction of hades252_cipher_*_dev above (and of tests/cipher_model.py), recorded as the chain witnesses record the
  * sponge and Merkle openings: S = hades252_cipher_perms(M) = ceil(M / 4) + 1 permutations per message (0 for an invalid M),

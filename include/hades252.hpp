@@ -207,6 +207,40 @@ inline std::size_t cipher_decrypt(const BlsScalar *ciphers, const BlsScalar *key
     return rejected;
 }
 
+// The batched duplex sponge (dusk-safe's SAFE sponge; CONVENTION UNPINNED, include/hades252.h).  A call of an IO pattern is
+// one word: safe_absorb(n) / safe_squeeze(n).
+constexpr std::uint32_t safe_absorb(std::uint32_t n) { return HADES252_SAFE_ABSORB | n; }
+constexpr std::uint32_t safe_squeeze(std::uint32_t n) { return n; }
+struct SafePattern {
+    std::size_t n_in, n_out, n_perms;      // words absorbed / squeezed and permutations, per sponge
+};
+// Validates a pattern (no device needed); panics on an invalid one.
+inline SafePattern safe_pattern(const std::uint32_t *calls, std::size_t n_calls) {
+    SafePattern p{0, 0, 0};
+    check(hades252_safe_pattern(calls, n_calls, &p.n_in, &p.n_out, &p.n_perms), "safe_pattern");
+    return p;
+}
+// Host memory: in n_msgs x n_in, out n_msgs x n_out scalars, message-major.
+inline void safe_hash(const BlsScalar *in, std::size_t n_msgs, const std::uint32_t *calls, std::size_t n_calls,
+                      const BlsScalar &tag, BlsScalar *out) {
+    check(hades252_safe_hash(reinterpret_cast<const std::uint64_t *>(in), n_msgs, calls, n_calls, tag.limbs,
+                             reinterpret_cast<std::uint64_t *>(out)), "safe_hash");
+}
+// DEVICE memory, enqueued on `stream`: the whole pattern in one launch, or call by call on the 160-byte states of
+// hades252_sponge_init_dev with a caller-owned cursor (0 = fresh) that moves with every call.
+inline void safe_hash_dev(const void *d_in, std::size_t n_msgs, const std::uint32_t *calls, std::size_t n_calls,
+                          const BlsScalar &tag, void *d_out, void *stream = nullptr) {
+    check(hades252_safe_hash_dev(d_in, n_msgs, calls, n_calls, tag.limbs, d_out, stream), "safe_hash_dev");
+}
+inline void safe_absorb_dev(void *d_states, std::size_t n_states, const void *d_in, std::size_t len, std::uint32_t &cursor,
+                            void *stream = nullptr) {
+    check(hades252_safe_absorb_dev(d_states, n_states, d_in, len, &cursor, stream), "safe_absorb_dev");
+}
+inline void safe_squeeze_dev(void *d_states, std::size_t n_states, std::size_t len, void *d_out, std::uint32_t &cursor,
+                             void *stream = nullptr) {
+    check(hades252_safe_squeeze_dev(d_states, n_states, len, d_out, &cursor, stream), "safe_squeeze_dev");
+}
+
 // Gadget witnesses of permutation chains, DEVICE memory (e.g. DeviceBuffer::ptr()), enqueued on `stream`
 // (include/hades252.h): permutation (s, i) is record s * n + i; d_inputs gets S * n states, d_wires 972 planes of S * n
 // scalars -- what hades252_perm_witness_dev writes for those states.
