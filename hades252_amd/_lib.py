@@ -147,6 +147,12 @@ SIGNATURES = {
     "hades252_safe_absorb_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, POINTER(ctypes.c_uint32), c_void_p]),
     "hades252_safe_squeeze_dev": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, POINTER(ctypes.c_uint32), c_void_p]),
     "hades252_safe_hash": (c_int, [c_void_p, c_size_t, POINTER(ctypes.c_uint32), c_size_t, POINTER(c_uint64), c_void_p]),
+    "hades252_safe_witness_dev": (c_int, [c_void_p, c_size_t, POINTER(ctypes.c_uint32), c_size_t, POINTER(c_uint64), c_void_p,
+                                          c_void_p, c_void_p, c_void_p]),
+    "hades252_safe_absorb_witness_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, POINTER(ctypes.c_uint32), c_void_p,
+                                                 c_void_p, c_size_t, POINTER(c_size_t), c_void_p]),
+    "hades252_safe_squeeze_witness_dev": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, POINTER(ctypes.c_uint32), c_void_p,
+                                                  c_void_p, c_size_t, POINTER(c_size_t), c_void_p]),
     "hades252_gen_b_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_uint64, c_void_p]),
     "hades252_gen_a_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_void_p]),
     "hades252_digest_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_void_p, c_void_p]),

@@ -1,5 +1,6 @@
 // abi_witness.hpp -- C ABI, device-resident data: gadget witnesses of the sponge (f1), of Merkle openings (f2) and of the
-// cipher (f5), the permutation chains of row f4.  Every argument rule is checked before the device is touched;
+// cipher (f5), of the duplex sponge (f9), the permutation chains of row f4.  Every argument rule is checked before the
+// device is touched;
 // include/hades252.h holds the contracts.
 #pragma once
 
@@ -134,6 +135,76 @@ int hades252_cipher_decrypt_witness_dev(const void *d_ciphers, const void *d_key
         return HADES252_ERR_INVALID_ARG;
     return cipher_witness_launch(true, d_ciphers, d_keys, d_nonces, n_msgs, msg_len, domain_mont, d_inputs, d_wires, d_msgs,
                                  d_ok, d_rejected, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+// ---- gadget witnesses of the duplex sponge (f9): k_witness_duplex, one sponge per lane -------------------------------
+// (after abi_safe.hpp: its planner, its cursor rule and its argument rules are reused).  There is no one-per-wave latency
+// form, as for the other chain witnesses: every batch size runs per lane.
+
+// arguments already checked: n >= 1, total_steps * n <= 2^30, step0 + plan.n_perms <= total_steps (so all pass as 32-bit).
+// d_states == NULL: fresh sponges [tag, 0, 0, 0, 0] that end with the launch (plan.n_perms >= 1).
+static int safe_witness_launch(const void *d_in, void *d_out, void *d_states, size_t n, const SafePlan &plan, uint32_t cursor,
+                               const Fr &tag, void *d_inputs, void *d_wires, size_t step0, size_t total_steps, hipStream_t s) {
+    hipLaunchKernelGGL(k_witness_duplex, dim3(blocks_for(n)), dim3(kBlock), 0, s, (const uint8_t *)d_in, (uint8_t *)d_out,
+                       (uint8_t *)d_states, (uint32_t)n, (uint32_t)plan.n_in, (uint32_t)plan.n_out, plan.calls, plan.n_calls,
+                       cursor, plan.n_perms, (uint32_t)step0, (uint32_t)total_steps, tag, (uint8_t *)d_inputs,
+                       (uint8_t *)d_wires);
+    HIP_TRY(hipGetLastError());
+    return HADES252_OK;
+}
+
+// one streaming call with its records: the rules of safe_stream (abi_safe.hpp) and of the chain witnesses; *cursor and
+// *step move on success only
+static int safe_witness_stream(void *d_states, size_t n_states, const void *d_in, void *d_out, size_t len, uint32_t kind,
+                               uint32_t *cursor, void *d_inputs, void *d_wires, size_t total_steps, size_t *step,
+                               void *stream) {
+    if (n_states == 0) return HADES252_OK;
+    const void *d_words = kind ? d_in : d_out;
+    if (d_states == nullptr || d_words == nullptr || cursor == nullptr || len == 0 || len > HADES252_SAFE_MAX_WORDS ||
+        n_states > kMaxLaunchRecords || misaligned(d_states) || misaligned(d_words) || !safe_cursor_ok(*cursor))
+        return HADES252_ERR_INVALID_ARG;
+    if (d_inputs == nullptr || d_wires == nullptr || misaligned(d_inputs) || misaligned(d_wires) || step == nullptr ||
+        total_steps > kMaxLaunchRecords / n_states || *step > total_steps)
+        return HADES252_ERR_INVALID_ARG;
+    const uint32_t call = kind | (uint32_t)len;
+    SafePlan plan;
+    if (!safe_plan(&call, 1, *cursor, plan) || plan.n_perms > total_steps - *step) return HADES252_ERR_INVALID_ARG;
+    const int rc = safe_witness_launch(d_in, d_out, d_states, n_states, plan, *cursor, Fr{}, d_inputs, d_wires, *step,
+                                       total_steps, (hipStream_t)stream);
+    if (rc == HADES252_OK) {
+        *cursor = plan.cursor_out;
+        *step += plan.n_perms;
+    }
+    return rc;
+}
+
+extern "C" {
+
+int hades252_safe_witness_dev(const void *d_in, size_t n_msgs, const uint32_t *calls, size_t n_calls,
+                              const uint64_t tag_mont[4], void *d_inputs, void *d_wires, void *d_out, void *stream) {
+    if (n_msgs == 0) return HADES252_OK;
+    SafePlan plan;
+    if (d_in == nullptr || tag_mont == nullptr || n_msgs > kMaxLaunchRecords || misaligned(d_in) || misaligned(d_out) ||
+        d_inputs == nullptr || d_wires == nullptr || misaligned(d_inputs) || misaligned(d_wires) ||
+        !safe_pattern_plan(calls, n_calls, plan))
+        return HADES252_ERR_INVALID_ARG;
+    if (plan.n_perms > kMaxLaunchRecords / n_msgs) return HADES252_ERR_INVALID_ARG;     // S * n_msgs records, at most 2^30
+    return safe_witness_launch(d_in, d_out, nullptr, n_msgs, plan, 0, fr_from_u64(tag_mont), d_inputs, d_wires, 0,
+                               plan.n_perms, (hipStream_t)stream);
+}
+
+int hades252_safe_absorb_witness_dev(void *d_states, size_t n_states, const void *d_in, size_t len, uint32_t *cursor,
+                                     void *d_inputs, void *d_wires, size_t total_steps, size_t *step, void *stream) {
+    return safe_witness_stream(d_states, n_states, d_in, nullptr, len, HADES252_SAFE_ABSORB, cursor, d_inputs, d_wires,
+                               total_steps, step, stream);
+}
+
+int hades252_safe_squeeze_witness_dev(void *d_states, size_t n_states, size_t len, void *d_out, uint32_t *cursor,
+                                      void *d_inputs, void *d_wires, size_t total_steps, size_t *step, void *stream) {
+    return safe_witness_stream(d_states, n_states, nullptr, d_out, len, 0, cursor, d_inputs, d_wires, total_steps, step,
+                               stream);
 }
 
 }  // extern "C"

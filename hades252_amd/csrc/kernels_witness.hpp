@@ -312,3 +312,109 @@ __global__ void __launch_bounds__(kBlock, 3) k_witness_cipher(const uint8_t *__r
         if ((threadIdx.x & (kWave - 1)) == 0 && rej != 0 && p.rejected != nullptr) atomicAdd(p.rejected, (int)__popcll(rej));
     }
 }
+
+// Duplex sponge witness (the construction of k_safe, kernels_safe.hpp; CONVENTION UNPINNED): lane i runs sponge i through
+// the n_perms permutations the host counted for the calls (abi_safe.hpp), the t-th of them record rec = (step0 + t) * n + i
+// of planes of length total * n.  Between two permutations a sponge emits j words and then adds k words (one SafeStep of
+// the unchanged, wave-uniform walk): the emitted words are read from the state just loaded (to out, per lane, when out is
+// there), the added ones go in with fr_add from a per-lane load_word, as k_witness_sponge reads its blocks -- the traffic
+// is ~1 % of a record's 31 KB of wires, so no LDS slab.  As in the sibling chains the state between permutations is the
+// last round's r2 wires in memory, read back by the lane that wrote them; the state of the call's first step is read from
+// `states` (streaming) or, states == NULL (one-shot: a fresh sponge that ends with the launch), from the lane's first input
+// record, where [tag, 0, 0, 0, 0] is parked first.  After the last permutation the loop body runs once more: the final
+// step (the last emits; in streaming also trailing adds), and the five state words go to `states` instead of an input
+// record -- ONE store site with a selected destination, so that nothing but the round loop consumes st[] after the step.
+// A call without a permutation (streaming, n_perms = 0) writes no record at all.
+// SGPR budget: the round loop leaves a chain a handful of SGPRs.  The chain carries the step t, n, n_perms, step0, total
+// and the two pointers the rounds write.  Everything the step alone needs is parked in LDS and read back at the top of
+// every step behind an opaque index: the constants of the launch once per block, the walk and the two word offsets in a
+// slot per wave (waves of a block do not run in lockstep: no block barrier belongs inside the loop).  The parked values
+// are uniform: every lane of a wave stores the same value and reads back only what it wrote itself, so no cross-lane
+// ordering arises; they are left as the per-lane values the LDS read returns.  The 64 call words are copied to LDS once
+// (static indices, one thread, the barrier before the loop) and indexed there: a dynamically indexed 256-byte by-value
+// argument costs the round loop its registers.  No one-per-wave latency form, as for the other chain witnesses.
+struct DuplexWitnessConst {
+    const uint8_t *in;
+    uint8_t *out, *states;
+    uint32_t n_in, n_out, n_calls, pad;
+};
+struct DuplexWitnessSlot {
+    SafeWalk walk;
+    uint32_t in_off, out_off;
+};
+
+__global__ void __launch_bounds__(kBlock, 3) k_witness_duplex(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+                                                              uint8_t *states, uint32_t n, uint32_t n_in, uint32_t n_out,
+                                                              SafeCalls calls, uint32_t n_calls, uint32_t cursor,
+                                                              uint32_t n_perms, uint32_t step0, uint32_t total, Fr tag,
+                                                              uint8_t *__restrict__ inputs, uint8_t *__restrict__ wires) {
+    __shared__ SafeCalls parked_calls;
+    __shared__ DuplexWitnessConst parked_const[1];
+    __shared__ DuplexWitnessSlot parked_slot[kWavesPerBlock];
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < HADES252_SAFE_MAX_CALLS; c++) parked_calls.c[c] = calls.c[c];
+        parked_const[0] = DuplexWitnessConst{in, out, states, n_in, n_out, n_calls, 0};
+    }
+    __syncthreads();
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    const bool live = i < n;
+    const int wave = threadIdx.x / kWave;
+    {
+        DuplexWitnessSlot first;
+        first.walk = safe_begin(parked_calls, cursor);
+        first.in_off = first.out_off = 0;
+        parked_slot[wave] = first;
+    }
+    if (states == nullptr && live) {                    // one-shot: n_perms >= 1, so the record exists
+        uint8_t *park = inputs + ((size_t)step0 * n + i) * 160;
+        store_word(park, tag);
+#pragma unroll
+        for (int w = 1; w < 5; w++) store_word(park + w * 32, zero_word());
+    }
+#pragma unroll 1
+    for (uint32_t t = 0;; t++) {
+        int z = 0;
+        asm volatile("" : "+s"(z));
+        const DuplexWitnessConst k = parked_const[z];
+        DuplexWitnessSlot slot = parked_slot[wave + z];
+        const size_t plane = (size_t)total * n;
+        const size_t rec = (size_t)(step0 + t) * n + i;
+        // the previous state: the caller's or the parked one, or the previous permutation's output (r2 of its last round)
+        const uint8_t *src = t != 0             ? wires + ((size_t)kWitnessLastRow * plane + rec - n) * 32
+                             : k.states != nullptr ? k.states + (size_t)i * 160
+                                                   : inputs + rec * 160;
+        const size_t stride = t != 0 ? 2 * plane * 32 : 32;
+        Fr st[5];
+#pragma unroll
+        for (int w = 0; w < 5; w++) st[w] = live ? load_word(src + w * stride) : zero_word();
+        const SafeStep s = safe_step(parked_calls, k.n_calls, slot.walk);
+        if (s.j > 0 && live && k.out != nullptr) {      // emit: read, not changed
+            uint8_t *dst = k.out + ((size_t)i * k.n_out + slot.out_off) * 32;
+#pragma unroll
+            for (int p = 0; p < 4; p++)
+                if (p >= s.e0 && p < s.e0 + s.j) store_word(dst + (p - s.e0) * 32, st[1 + p]);
+        }
+        if (s.k > 0) {                                  // absorb: the gadget's add gates
+            const uint8_t *from = k.in + (live ? ((size_t)i * k.n_in + slot.in_off) * 32 : 0);
+#pragma unroll
+            for (int p = 0; p < 4; p++)
+                if (p >= s.a0 && p < s.a0 + s.k)
+                    st[1 + p] = fr_add(st[1 + p], live ? load_word(from + (p - s.a0) * 32) : zero_word());
+        }
+        slot.out_off += s.j;
+        slot.in_off += s.k;
+        safe_permuted(parked_calls, k.n_calls, slot.walk);     // (after the last permutation the walk is not read again)
+        parked_slot[wave + z] = slot;
+        const bool last = t == n_perms;
+        uint8_t *dst = last ? k.states + (size_t)i * 160 : inputs + rec * 160;
+        if (live && !(last && k.states == nullptr)) {
+#pragma unroll
+            for (int w = 0; w < 5; w++) store_word(dst + w * 32, st[w]);
+        }
+        if (last) break;
+        F29 y[5];
+        witness_enter(st, y);
+        witness_rounds(y, wires, plane, rec, live);
+    }
+}

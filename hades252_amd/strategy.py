@@ -1077,6 +1077,95 @@ class SafeSponge:
             raise ValueError("SafeSponge.finish: the IO pattern still expects %s(%d)" % tuple(self._todo[0]))
 
 
+def safe_witness(inputs_t, pattern, tag_mont: int):
+    """Gadget witness of the duplex sponge, the whole pattern in one launch (``hades252_safe_witness_dev``; the arguments of
+    ``safe_hash``).  Returns (wires [972, S, n, 4], inputs [S, n, 5, 4], out [n, n_out, 4]) with S the pattern's
+    permutations per sponge: inputs[s, i] enters permutation s of sponge i, wires.reshape(972, S * n, 4) ==
+    perm_witness(inputs) byte for byte, and out is what ``safe_hash`` returns."""
+    import torch
+    n_in, n_out, S = safe_pattern(pattern)
+    arr, k = _safe_calls(pattern, "safe_witness")
+    ptr, n_words, dev = _dev_buffer(inputs_t, 32, "safe_witness")
+    if n_words % n_in:
+        raise ValueError("safe_witness: %d scalars are not a whole number of inputs of %d" % (n_words, n_in))
+    n = n_words // n_in
+    wires = torch.empty((witness_wires(), S, n, 4), dtype=torch.int64, device=dev)
+    inputs = torch.empty((S, n, 5, 4), dtype=torch.int64, device=dev)
+    out = torch.empty((n, n_out, 4), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().hades252_safe_witness_dev(ptr, n, arr, k, _tag_arr(tag_mont), inputs.data_ptr(), wires.data_ptr(),
+                                                   out.data_ptr(), _stream_ptr(dev)), "safe_witness")
+    return wires, inputs, out
+
+
+class SafeWitnessSponge(SafeSponge):
+    """A ``SafeSponge`` that also records the permutations its calls run (``hades252_safe_absorb_witness_dev`` /
+    ``_squeeze_witness_dev``): it owns the two record buffers, sized for the pattern's S permutations per sponge, and the
+    step counter.  After ``finish`` (which also demands that all S steps were recorded) ``wires`` [972, S, n, 4] and
+    ``inputs`` [S, n, 5, 4] hold what ``safe_witness`` returns for the same words."""
+
+    def __init__(self, n: int, pattern, tag_mont: int, device="cuda"):
+        import torch
+        super().__init__(n, pattern, tag_mont, device)
+        self._steps = safe_pattern(pattern)[2]
+        self._step = ctypes.c_size_t(0)
+        dev = self.states.device
+        self._wires = torch.empty((witness_wires(), self._steps, n, 4), dtype=torch.int64, device=dev)
+        self._inputs = torch.empty((self._steps, n, 5, 4), dtype=torch.int64, device=dev)
+        self._finished = False
+
+    def absorb(self, t) -> None:
+        """t: n x k scalars (state-major) for the next k words of the current absorb call."""
+        import torch
+        n = self.states.shape[0]
+        ptr, n_words, dev = _dev_buffer(t, 32, "SafeWitnessSponge.absorb")
+        _same_device("SafeWitnessSponge.absorb", self.states.device, dev)
+        if n == 0 or n_words % n:
+            raise ValueError("SafeWitnessSponge.absorb: %d scalars do not split evenly over %d sponges" % (n_words, n))
+        k = n_words // n
+        self._take("absorb", k)
+        with torch.cuda.device(dev):
+            check(_lib.lib().hades252_safe_absorb_witness_dev(self.states.data_ptr(), n, ptr, k, ctypes.byref(self._cursor),
+                                                              self._inputs.data_ptr(), self._wires.data_ptr(), self._steps,
+                                                              ctypes.byref(self._step), _stream_ptr(dev)),
+                  "SafeWitnessSponge.absorb")
+        self._took(k)
+
+    def squeeze(self, k: int):
+        """-> [n, k, 4] int64: the next k words of the current squeeze call."""
+        import torch
+        n, dev = self.states.shape[0], self.states.device
+        self._take("squeeze", k)
+        out = torch.empty((n, k, 4), dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            check(_lib.lib().hades252_safe_squeeze_witness_dev(self.states.data_ptr(), n, k, out.data_ptr(),
+                                                               ctypes.byref(self._cursor), self._inputs.data_ptr(),
+                                                               self._wires.data_ptr(), self._steps, ctypes.byref(self._step),
+                                                               _stream_ptr(dev)), "SafeWitnessSponge.squeeze")
+        self._took(k)
+        return out
+
+    def finish(self) -> None:
+        """The pattern must be used up; ``wires`` and ``inputs`` are readable afterwards."""
+        super().finish()
+        if self.states.shape[0] != 0 and self._step.value != self._steps:
+            raise ValueError("SafeWitnessSponge.finish: %d of %d steps recorded" % (self._step.value, self._steps))
+        self._finished = True
+
+    def _records(self, t):
+        if not self._finished:
+            raise ValueError("SafeWitnessSponge: the records are complete after finish() only")
+        return t
+
+    @property
+    def wires(self):
+        return self._records(self._wires)
+
+    @property
+    def inputs(self):
+        return self._records(self._inputs)
+
+
 GEN_SEED = 0x4861646573323532
 
 

@@ -550,6 +550,39 @@ int hades252_cipher_decrypt_witness_dev(const void *d_ciphers, const void *d_key
                                         size_t msg_len, const uint64_t domain_mont[4], void *d_inputs, void *d_wires,
                                         void *d_msgs, uint8_t *d_ok, int *d_rejected, void *stream);
 
+/* ---- gadget witnesses of the duplex sponge (f9): the fourth chain of row f4, one-shot and streaming ---- CONVENTION UNPINNED
+ * The construction of hades252_safe_*_dev above (and of tests/safe_model.py), recorded as the other chain witnesses are:
+ * a batch of n sponges that run S permutations each is S * n records, rec = s * n + i (step-major); d_inputs receives S * n
+ * states of 160 B, d_wires 972 planes of S * n scalars, wire-major.
+ *   inputs[0][i] = [tag, 0, 0, 0, 0] with the words absorbed before the first permutation added at their positions;
+ *   inputs[s][i] (s >= 1) = the output of permutation (s - 1, i) with the words absorbed between permutations s - 1 and s
+ *   added at their positions.  Words squeezed in between are read, not changed: the gadget's add gates are the consumer's,
+ *   the inputs carry their values.
+ * Defining property: wires == hades252_perm_witness_dev(inputs) byte for byte, the S * n states taken as one flat batch.
+ * The output of the last permutation is r2 of the last round of record (S - 1) n + i.
+ * One-shot (hades252_safe_witness_dev): the whole IO pattern of hades252_safe_hash_dev, S = n_perms of
+ * hades252_safe_pattern(calls) (a valid pattern has S >= 1).  d_out (n x n_out, may be NULL: not written) is byte for byte
+ * what hades252_safe_hash_dev writes; d_in is not modified.
+ * Streaming (hades252_safe_absorb_witness_dev / hades252_safe_squeeze_witness_dev): d_states, *cursor, d_in, d_out and len
+ * mean exactly what they mean for hades252_safe_absorb_dev / hades252_safe_squeeze_dev, and after the call d_states, d_out
+ * and *cursor hold exactly the bytes the plain call would have left.  d_inputs / d_wires are sized for total_steps steps
+ * (plane length total_steps * n_states); the t-th permutation a call runs is step *step + t.  A call that runs q
+ * permutations needs *step + q <= total_steps and adds q to *step on success only (q = 0 is legal: nothing is recorded).
+ * Any split of a pattern into streaming witness calls with total_steps = the pattern's S gives the d_inputs, d_wires and
+ * output bytes of the one-shot call.  The crate's cipher is composed over them as over the plain calls.
+ * One sponge per lane whatever the batch size, the state carried across its steps: one sponge costs S x the latency of
+ * one perm_witness lane; there is no one-per-wave latency form, as for the other chain witnesses.
+ * Rules, all decided before the device is touched: those of the plain calls (n_msgs / n_states = 0 is a no-op success: the
+ * cursor and the step stay), and d_inputs / d_wires non-NULL and 16-byte aligned, d_out of the one-shot call 16-byte
+ * aligned when not NULL, step non-NULL, S * n_msgs (one-shot) or total_steps * n_states (streaming) at most 2^30,
+ * *step + q <= total_steps.  Input words canonical and unchecked, as for hades252_safe_hash_dev. */
+int hades252_safe_witness_dev(const void *d_in, size_t n_msgs, const uint32_t *calls, size_t n_calls,
+                              const uint64_t tag_mont[4], void *d_inputs, void *d_wires, void *d_out, void *stream);
+int hades252_safe_absorb_witness_dev(void *d_states, size_t n_states, const void *d_in, size_t len, uint32_t *cursor,
+                                     void *d_inputs, void *d_wires, size_t total_steps, size_t *step, void *stream);
+int hades252_safe_squeeze_witness_dev(void *d_states, size_t n_states, size_t len, void *d_out, uint32_t *cursor,
+                                      void *d_inputs, void *d_wires, size_t total_steps, size_t *step, void *stream);
+
 /* ---- synthetic inputs and digests (benchmark / verification plumbing) --------------------- */
 /* Generator B: scalar e (global element index first_elem + k) gets 4 splitmix64 limbs, top limb
  * masked to 62 bits (always < p); see DESIGN.md.  Stateless, so shards generate independently. */

@@ -278,6 +278,27 @@ inline void cipher_decrypt_witness(const void *d_ciphers, const void *d_keys, co
                                               d_msgs, d_ok, d_rejected, stream), "cipher_decrypt_witness");
 }
 
+// The duplex sponge with its records: the whole pattern (S = safe_pattern(..).n_perms steps; d_out may be nullptr), or
+// call by call -- safe_absorb_dev / safe_squeeze_dev that also record the permutations they run as steps step, step + 1, ..
+// of buffers sized for total_steps steps; `step` moves with every call, like the cursor.
+inline void safe_witness(const void *d_in, std::size_t n_msgs, const std::uint32_t *calls, std::size_t n_calls,
+                         const BlsScalar &tag, void *d_inputs, void *d_wires, void *d_out = nullptr, void *stream = nullptr) {
+    check(hades252_safe_witness_dev(d_in, n_msgs, calls, n_calls, tag.limbs, d_inputs, d_wires, d_out, stream),
+          "safe_witness");
+}
+inline void safe_absorb_witness_dev(void *d_states, std::size_t n_states, const void *d_in, std::size_t len,
+                                    std::uint32_t &cursor, void *d_inputs, void *d_wires, std::size_t total_steps,
+                                    std::size_t &step, void *stream = nullptr) {
+    check(hades252_safe_absorb_witness_dev(d_states, n_states, d_in, len, &cursor, d_inputs, d_wires, total_steps, &step,
+                                           stream), "safe_absorb_witness_dev");
+}
+inline void safe_squeeze_witness_dev(void *d_states, std::size_t n_states, std::size_t len, void *d_out,
+                                     std::uint32_t &cursor, void *d_inputs, void *d_wires, std::size_t total_steps,
+                                     std::size_t &step, void *stream = nullptr) {
+    check(hades252_safe_squeeze_witness_dev(d_states, n_states, len, d_out, &cursor, d_inputs, d_wires, total_steps, &step,
+                                            stream), "safe_squeeze_witness_dev");
+}
+
 // What the library caches (pipes: streams, chunk buffers, staging memory) and which kernel a batch size gets.
 inline void trim() { check(hades252_trim(), "trim"); }
 inline std::size_t pool_bytes() { return hades252_pool_bytes(); }

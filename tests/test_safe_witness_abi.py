@@ -1,0 +1,218 @@
+"""CPU tier: the boundary of the duplex sponge witnesses (hades252_safe_witness_dev, hades252_safe_{absorb,squeeze}_witness_dev)
+without a GPU -- the symbols are declared, bound and exported; the header states the contract; every argument rule answers
+before the device is touched and leaves *cursor and *step alone; the Python layer checks types; the C++ wrappers compile and
+link; the new code leaves the keys of the committed counter records alone; and the code object of k_witness_duplex in the
+built library has k_perm_witness's budget."""
+import ctypes
+import json
+import os
+import re
+import subprocess
+
+import pytest
+
+import safe_model as M
+from safe_model import A, Q
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "hades252_amd", "csrc")
+SYMS = ["hades252_safe_witness_dev", "hades252_safe_absorb_witness_dev", "hades252_safe_squeeze_witness_dev"]
+INVALID = -1
+
+# fake, never dereferenced: every call below must be refused by the argument checks (or be a no-op success)
+PTR = 0x10000          # 16-byte aligned
+MIS = PTR + 8          # misaligned
+
+
+def _calls(pattern):
+    words = M.encode(pattern)
+    return (ctypes.c_uint32 * max(len(words), 1))(*words), len(words)
+
+
+def _tag():
+    return (ctypes.c_uint64 * 4)(1, 2, 3, 4)
+
+
+def test_symbols_are_declared_bound_and_exported(hades_lib):
+    from hades252_amd import _lib
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hades252.h")).read(), flags=re.S)
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    for s in SYMS:
+        assert re.search(r"\b%s\s*\(" % s, text), s
+        assert s in _lib.SIGNATURES, s
+        assert hasattr(raw, s), s
+
+
+def test_header_states_the_contract():
+    text = open(os.path.join(ROOT, "include", "hades252.h")).read()
+    start = text.index("gadget witnesses of the duplex sponge")
+    block = text[start:text.index("int hades252_safe_witness_dev")]
+    for needle in ("CONVENTION UNPINNED", "rec = s * n", "hades252_perm_witness_dev(inputs) byte for byte", "2^30",
+                   "may be NULL", "*step + q <= total_steps", "on success only", "read, not changed",
+                   "no one-per-wave latency form"):
+        assert needle in block, needle
+    # after the cipher-witness section, which follows the plain duplex sponge
+    assert text.index("batched duplex sponge") < text.index("gadget witnesses of the cipher") < start
+    assert text.index("int hades252_cipher_decrypt_witness_dev(") < start
+
+
+def test_one_shot_argument_rules(hades_lib):
+    f = hades_lib.hades252_safe_witness_dev
+    arr, k = _calls([A(3), Q(2), A(2), Q(1)])                      # S = 2
+    tag = _tag()
+
+    def call(d_in=PTR, n=5, calls=arr, n_calls=k, t=tag, inp=PTR, wires=PTR, out=None):
+        return f(d_in, n, calls, n_calls, t, inp, wires, out, None)
+
+    assert call(d_in=None, n=0, calls=None, n_calls=0, t=None, inp=None, wires=None) == 0          # n = 0: a no-op
+    assert call(n=0, out=MIS) == 0
+    for kw in ({"d_in": None}, {"t": None}, {"calls": None}, {"n_calls": 0}, {"n_calls": 65}, {"d_in": MIS}, {"out": MIS},
+               {"inp": None}, {"wires": None}, {"inp": MIS}, {"wires": MIS}, {"n": (1 << 30) + 1},
+               {"n": (1 << 29) + 1}):                                # 2 permutations x (2^29 + 1) > 2^30 records
+        assert call(**kw) == INVALID, kw
+    for bad in ([Q(1)], [A(1)], [A(1), Q(1), A(1)], [A(0), Q(1)], [A(1), Q(0)], [A((1 << 20) + 1), Q(1)]):
+        barr, bk = _calls(bad)
+        assert call(calls=barr, n_calls=bk) == INVALID, bad
+    s16, k16 = _calls([A(1), Q(64)])                                # S = 16: 2^26 sponges are 2^30 records, one more is not
+    assert call(calls=s16, n_calls=k16, n=(1 << 26) + 1) == INVALID
+
+
+@pytest.mark.parametrize("kind", ["absorb", "squeeze"])
+def test_streaming_argument_rules_leave_cursor_and_step_alone(hades_lib, kind):
+    absorb = kind == "absorb"
+    f = hades_lib.hades252_safe_absorb_witness_dev if absorb else hades_lib.hades252_safe_squeeze_witness_dev
+
+    def call(states=PTR, n=4, words=PTR, length=3, cur=None, inp=PTR, wires=PTR, total=8, step=None):
+        if absorb:
+            return f(states, n, words, length, cur, inp, wires, total, step, None)
+        return f(states, n, length, words, cur, inp, wires, total, step, None)
+
+    for start in (0, 2 | (4 << 4), 1 << 4, 4 | (4 << 4)):          # fresh, after absorbs (a full block last), after a squeeze
+        for step0 in (0, 3):
+            cur, step = ctypes.c_uint32(start), ctypes.c_size_t(step0)
+            c, s = ctypes.byref(cur), ctypes.byref(step)
+            assert call(n=0, cur=c, step=s) == 0                    # a no-op: the cursor and the step stay
+            assert call(states=None, n=0, words=None, cur=None, inp=None, wires=None, step=None) == 0
+            for kw in ({"states": None}, {"words": None}, {"states": MIS}, {"words": MIS}, {"length": 0},
+                       {"length": (1 << 20) + 1}, {"n": (1 << 30) + 1}, {"cur": None}, {"inp": None}, {"wires": None},
+                       {"inp": MIS}, {"wires": MIS}, {"step": None},
+                       {"n": 1 << 28, "total": 5},                   # 5 x 2^28 > 2^30 records
+                       {"total": step0 - 1 if step0 else 0, "length": 9},   # *step (+ q) past total_steps
+                       {"total": step0 + 1, "length": 9}):           # 9 words run at least 2 permutations: one step of room
+                kw = dict({"cur": c, "step": s}, **kw)
+                assert call(**kw) == INVALID, (kind, start, step0, kw)
+                assert cur.value == start and step.value == step0, kw
+    for bad in (5, 1 | (2 << 4), 5 << 4, 1 << 8):                   # not a cursor this library hands out
+        cur, step = ctypes.c_uint32(bad), ctypes.c_size_t(0)
+        assert call(cur=ctypes.byref(cur), step=ctypes.byref(step)) == INVALID, bad
+        assert cur.value == bad and step.value == 0
+
+
+def test_python_layer_checks_types_and_patterns():
+    import numpy as np
+    from hades252_amd import strategy as H
+    assert issubclass(H.SafeWitnessSponge, H.SafeSponge)
+    for name in ("absorb", "squeeze", "finish", "wires", "inputs"):
+        assert hasattr(H.SafeWitnessSponge, name), name
+    with pytest.raises(TypeError):                               # host memory is not a device batch
+        H.safe_witness(np.zeros((2, 5, 4), dtype=np.uint64), [A(3), Q(2), A(2), Q(1)], 1)
+    with pytest.raises(ValueError):
+        H.safe_witness(np.zeros((2, 5, 4), dtype=np.uint64), [Q(1)], 1)
+
+
+def test_cpp_wrappers_compile_and_link(hades_lib, tmp_path):
+    src = tmp_path / "safe_witness.cpp"
+    src.write_text(r'''
+#include "hades252.hpp"
+#include <cstdio>
+int main() {
+    const std::uint32_t calls[2] = {dusk_hades::safe_absorb(3), dusk_hades::safe_squeeze(2)};
+    std::printf("%zu\n", dusk_hades::safe_pattern(calls, 2).n_perms);
+    dusk_hades::BlsScalar tag{};
+    std::uint32_t cursor = 0;
+    std::size_t step = 0;
+    try {
+        dusk_hades::safe_witness(nullptr, 3, calls, 2, tag, nullptr, nullptr);
+    } catch (const dusk_hades::HadesPanic &e) {                  // refused before the device
+        std::printf("%s\n", e.what());
+    }
+    try {
+        dusk_hades::safe_absorb_witness_dev(nullptr, 3, nullptr, 3, cursor, nullptr, nullptr, 1, step);
+    } catch (const dusk_hades::HadesPanic &e) {
+        std::printf("%s\n", e.what());
+    }
+    try {
+        dusk_hades::safe_squeeze_witness_dev(nullptr, 3, 2, nullptr, cursor, nullptr, nullptr, 1, step);
+    } catch (const dusk_hades::HadesPanic &e) {
+        std::printf("%s\n", e.what());
+    }
+    std::printf("%u %zu\n", cursor, step);
+    return 0;
+}
+''')
+    exe = tmp_path / "safe_witness"
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-L", CSRC,
+                    "-lhades252", "-Wl,-rpath," + CSRC, "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines()
+    assert out[0] == "1" and out[-1] == "0 0" and len(out) == 5, out
+
+
+def test_counter_records_stay_keyed():
+    """The duplex sponge witness lives in kernels_witness.hpp / abi_witness.hpp, outside build.device_source_hash and
+    perm_fast_hash, so bench.py keeps replaying its counter-backed traffic."""
+    from hades252_amd import build
+    new = {"kernels_witness.hpp", "abi_witness.hpp"}
+    assert new <= set(build.UNRECORDED_KERNEL_DEPS) and new <= set(build.DEPS)
+    assert not new & set(build.DEVICE_DEPS + build.LAUNCH_POLICY_DEPS + build.PERM_FAST_DEPS)
+    with open(os.path.join(ROOT, "profiles", "hbm_traffic.json")) as f:
+        rec = json.load(f)
+    assert rec["secondary_kernels"]["device_source_hash"] == build.device_source_hash()
+    assert json.dumps(rec).count(build.perm_fast_hash()) >= 1
+
+
+LLVM = os.environ.get("ROCM_LLVM_BIN", "/opt/rocm/llvm/bin")
+
+
+@pytest.fixture(scope="module")
+def code_object(hades_lib, tmp_path_factory):
+    """(resource metadata, disassembly) of the witness kernels, read from the gfx950 code object INSIDE the built library."""
+    tools = [os.path.join(LLVM, t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf", "llvm-objdump")]
+    if not all(os.path.exists(t) for t in tools):
+        pytest.skip("ROCm LLVM tools not available")
+    objcopy, bundler, readelf, objdump = tools
+    from hades252_amd import _lib
+    tmp_path = tmp_path_factory.mktemp("codeobj")
+    fat, co = tmp_path / "fatbin", tmp_path / "gfx950.co"
+    subprocess.run([objcopy, "--dump-section", ".hip_fatbin=%s" % fat, _lib.LIB_PATH, str(tmp_path / "scratch.so")],
+                   check=True)
+    subprocess.run([bundler, "--unbundle", "--type=o", "--input=%s" % fat, "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
+                    "--output=%s" % co], check=True)
+    notes = subprocess.run([readelf, "--notes", str(co)], check=True, capture_output=True, text=True).stdout
+    res = {}
+    for entry in re.split(r"^  - (?=\.)", notes, flags=re.M)[1:]:
+        m = re.search(r"^    \.name:\s+(\S+)", entry, re.M)
+        if m is None or "witness" not in m.group(1):
+            continue
+        res[m.group(1)] = {k: int(v) for k, v in re.findall(r"^\s*\.(\w+):\s+(\d+)$", entry, re.M)
+                           if k in ("agpr_count", "vgpr_count", "vgpr_spill_count", "sgpr_spill_count",
+                                    "private_segment_fixed_size", "group_segment_fixed_size")}
+    text = subprocess.run([objdump, "-d", str(co)], check=True, capture_output=True, text=True).stdout
+    parts = re.split(r"^[0-9a-f]+ <(\S+)>:$", text, flags=re.M)
+    bodies = {parts[i]: parts[i + 1] for i in range(1, len(parts), 2) if "witness" in parts[i]}
+    return res, bodies
+
+
+def test_duplex_witness_kernel_has_the_perm_witness_budget(code_object):
+    res, bodies = code_object
+    (perm,) = [k for k in bodies if "k_perm_witness" in k]
+    (name,) = [k for k in bodies if "k_witness_duplex" in k]     # one kernel: one-shot and streaming
+    for other in ("k_safe", "k_cipher", "k_witness_sponge", "k_witness_cipher", "k_perm_witness"):
+        assert other not in name                                 # the neighbours' tests count kernels by these substrings
+    ref = len(re.findall(r"\bv_mad_[iu]64_[iu]32\b", bodies[perm]))
+    mads = len(re.findall(r"\bv_mad_[iu]64_[iu]32\b", bodies[name]))
+    assert abs(mads - ref) <= 0.02 * ref, (name, mads, ref)      # ONE call site of the round loop
+    assert "scratch_" not in bodies[name]
+    r = res[name]
+    print(name, r, "v_mad", mads, "against", ref)
+    assert r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0, (name, r)
+    assert r["vgpr_count"] + r["agpr_count"] <= 152 and r["sgpr_spill_count"] <= 8, (name, r)
