@@ -17,7 +17,8 @@ __all__ = ["KERNELS", "TAG", "TAG4", "CAP", "SITES_PERM", "to_dev", "to_host", "
            "kernel_available", "each_state_is_input_or_output", "_record", "word_boundary_values", "ARK_SHA256", "MDS_SHA256",
            "blob_bytes", "EDGE_VALUES", "edge_scalars", "SENTINEL", "Guarded", "guarded_call", "FORM_SIZES", "LEVEL_SIZES",
            "sponge_form", "absorb_form", "level_form", "verify_form", "update_form", "form_family", "oracle_sponge_var",
-           "SPONGE_BUCKETS", "COUNT_GRID_RECORDS", "CATALOGUE_LANES", "catalogue_states", "placed_batches"]
+           "SPONGE_BUCKETS", "COUNT_GRID_RECORDS", "CATALOGUE_LANES", "catalogue_states", "placed_batches", "WIRES",
+           "mont_rows", "perm_many_over", "gadget_check", "assert_wires_are_perm_witness"]
 
 KERNELS = [1, 2, 3, 4, 5]   # HADES252_KERNEL_LITERAL, _FAST (one state per lane), _COOP (five waves per state), _LANES (one
                             # state per wave, elements spread over 16-lane rows), _ROWS (one state per row, four per wave)
@@ -273,3 +274,42 @@ def placed_batches(states, n, fill):
         b = fill.copy()
         b[lanes[:len(idx)]] = states[idx]
         yield b, lanes[:len(idx)], idx
+
+
+# ---------------------------------------------------------------------------------------------
+# the gadget witness families (perm_witness and the chains recorded over it): what each of them checks on its wires
+# ---------------------------------------------------------------------------------------------
+WIRES = 972                                      # wires per permutation record
+
+
+def mont_rows(vals):
+    """Canonical integers as in-memory Montgomery limbs, uint64 [len(vals), 4]."""
+    return np.array([limbs_of(S.to_mont(v)) for v in vals], dtype=np.uint64).reshape(-1, 4)
+
+
+def perm_many_over(oracle):
+    """A big-integer model's perm_many over the C oracle (Montgomery limbs in between)."""
+    def run(states):
+        if not states:
+            return []
+        out = oracle.perm_batch(mont_rows([v for st in states for v in st]).reshape(-1)).reshape(-1, 5, 4)
+        return [[S.from_mont(int_of(w)) for w in st] for st in out]
+    return run
+
+
+def gadget_check(wires_h, inputs_h, pairs):
+    """Records (s, i) of `pairs` against the spec's GadgetStrategy, wire for wire: host arrays wires_h [WIRES, S, n, 4]
+    and inputs_h [S, n, 5, 4]."""
+    for (s, i) in pairs:
+        st = [S.from_mont(int_of(inputs_h[s, i, w])) for w in range(5)]
+        spec = []
+        S.perm_gadget(st, spec)
+        got = [int_of(wires_h[g, s, i]) for g in range(WIRES)]
+        bad = [g for g in range(WIRES) if got[g] != S.to_mont(spec[g])]
+        assert not bad, ((s, i), bad[:8])
+
+
+def assert_wires_are_perm_witness(torch, H, inputs, wires):
+    """The defining property of every chain witness: wires == perm_witness(inputs), byte for byte."""
+    ref = H.perm_witness(inputs.reshape(-1, 20))
+    assert torch.equal(wires.reshape(WIRES, -1, 4), ref)

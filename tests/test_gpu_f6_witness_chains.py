@@ -15,35 +15,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import witness_chain_model as W  # noqa: E402
 from witness_chain_model import P, S  # noqa: E402
-from gpu_common import to_dev, to_host, TAG, CAP  # noqa: E402
+from gpu_common import to_dev, to_host, TAG, CAP, Guarded, gadget_check, mont_rows, perm_many_over  # noqa: E402
 from oracle_lib import limbs_of, int_of  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 0x5A5A5A5A5A5A5A5A
-NG = 64                                          # guard scalars behind every output buffer
-
-
-def _mont_rows(vals):
-    return np.array([limbs_of(S.to_mont(v)) for v in vals], dtype=np.uint64).reshape(-1, 4)
-
-
-def _perm_many(oracle):
-    """The model's perm_many over the C oracle (Montgomery limbs in between)."""
-    def run(states):
-        if not states:
-            return []
-        out = oracle.perm_batch(_mont_rows([v for st in states for v in st]).reshape(-1)).reshape(-1, 5, 4)
-        return [[S.from_mont(int_of(w)) for w in st] for st in out]
-    return run
-
-
-def _guarded(torch, n_scalars):
-    return torch.full(((n_scalars + NG) * 4,), GUARD, dtype=torch.int64, device="cuda")
-
-
-def _guard_ok(t, n_scalars):
-    return bool((t[n_scalars * 4:] == GUARD).all().item())
 
 
 def _messages(rng, n, msg_len):
@@ -57,16 +32,6 @@ def _messages(rng, n, msg_len):
     return out
 
 
-def _gadget_check(wires_h, inputs_h, S_, n, pairs):
-    for (s, i) in pairs:
-        st = [S.from_mont(int_of(inputs_h[s, i, w])) for w in range(5)]
-        spec = []
-        S.perm_gadget(st, spec)
-        got = [int_of(wires_h[g, s, i]) for g in range(W.WIRES)]
-        bad = [g for g in range(W.WIRES) if got[g] != S.to_mont(spec[g])]
-        assert not bad, ((s, i), bad[:8])
-
-
 @pytest.mark.parametrize("pad_mode", [0, 1])
 @pytest.mark.parametrize("msg_len", [0, 1, 3, 4, 5, 8, 13])
 def test_sponge_witness_against_model_and_perm_witness(torch_cuda, H, hades_lib, oracle, msg_len, pad_mode):
@@ -77,42 +42,38 @@ def test_sponge_witness_against_model_and_perm_witness(torch_cuda, H, hades_lib,
         cap = rng.choice([CAP, S.to_mont(rng.randrange(P))])
         S_ = W.sponge_blocks(msg_len, pad_mode)
         assert hades_lib.hades252_sponge_blocks(msg_len, pad_mode) == S_
-        host_msgs = _mont_rows([v for m in msgs for v in m]) if msg_len else np.zeros((0, 4), dtype=np.uint64)
+        host_msgs = mont_rows([v for m in msgs for v in m]) if msg_len else np.zeros((0, 4), dtype=np.uint64)
         dm = to_dev(torch, host_msgs.reshape(-1)) if msg_len else torch.zeros(0, dtype=torch.int64, device="cuda")
-        wires = _guarded(torch, W.WIRES * S_ * n)
-        inputs = _guarded(torch, 5 * S_ * n)
-        dig = _guarded(torch, n)
+        g_wires, g_inputs, g_dig = Guarded(torch, (W.WIRES, S_ * n, 4)), Guarded(torch, (S_ * n, 20)), Guarded(torch, (n, 4))
         capa = (ctypes.c_uint64 * 4)(*limbs_of(cap))
         rc = hades_lib.hades252_sponge_witness_dev(dm.data_ptr() if msg_len else None, n, msg_len, capa, pad_mode,
-                                                   inputs.data_ptr(), wires.data_ptr(), dig.data_ptr(), None)
+                                                   g_inputs.ptr, g_wires.ptr, g_dig.ptr, None)
         assert rc == 0
-        torch.cuda.synchronize()
-        assert _guard_ok(wires, W.WIRES * S_ * n) and _guard_ok(inputs, 5 * S_ * n) and _guard_ok(dig, n), (n, msg_len)
+        wires, inputs, dig = (g.check((n, msg_len)) for g in (g_wires, g_inputs, g_dig))    # guards whole, all written
         if msg_len:
             assert (to_host(dm) == host_msgs.reshape(-1)).all()                     # messages untouched
         # inputs against the model
-        exp_in, exp_out = W.sponge_inputs(msgs, S.from_mont(cap), pad_mode, _perm_many(oracle))
-        got_in = to_host(inputs)[:S_ * n * 20].reshape(S_, n, 5, 4)
-        assert (got_in == _mont_rows([v for step in exp_in for st in step for v in st]).reshape(S_, n, 5, 4)).all(), n
+        exp_in, exp_out = W.sponge_inputs(msgs, S.from_mont(cap), pad_mode, perm_many_over(oracle))
+        got_in = to_host(inputs).reshape(S_, n, 5, 4)
+        assert (got_in == mont_rows([v for step in exp_in for st in step for v in st]).reshape(S_, n, 5, 4)).all(), n
         # the defining property
-        inp_t = inputs[:S_ * n * 20].view(S_ * n, 20)
-        ref = H.perm_witness(inp_t)
-        assert torch.equal(wires[:W.WIRES * S_ * n * 4].view(W.WIRES, S_ * n, 4), ref), n
+        ref = H.perm_witness(inputs)
+        assert torch.equal(wires, ref), n
         # digests: hades252_sponge_hash_dev and the model
         ref_d = torch.empty((n, 4), dtype=torch.int64, device="cuda")
         assert hades_lib.hades252_sponge_hash_dev(dm.data_ptr() if msg_len else None, n, msg_len, capa, pad_mode,
                                                   ref_d.data_ptr(), None) == 0
-        assert torch.equal(dig[:n * 4].view(n, 4), ref_d), n
-        assert (to_host(ref_d).reshape(n, 4) == _mont_rows([o[1] for o in exp_out])).all()
+        assert torch.equal(dig, ref_d), n
+        assert (to_host(ref_d).reshape(n, 4) == mont_rows([o[1] for o in exp_out])).all()
         # sampled records against the spec's GadgetStrategy, wire for wire
-        wires_h = to_host(wires)[:W.WIRES * S_ * n * 4].reshape(W.WIRES, S_, n, 4)
+        wires_h = to_host(wires).reshape(W.WIRES, S_, n, 4)
         pairs = {(0, 0), (S_ - 1, n - 1), (rng.randrange(S_), rng.randrange(n))}
-        _gadget_check(wires_h, got_in, S_, n, sorted(pairs))
+        gadget_check(wires_h, got_in, sorted(pairs))
         if n == 65:                                   # the Python layer: same bytes, shapes [972, S, n, 4] / [S, n, 5, 4]
             src = dm.view(n, msg_len, 4) if msg_len else torch.zeros((n, 0, 4), dtype=torch.int64, device="cuda")
             pw, pi, pd = H.sponge_witness(src, msg_len, cap, pad_mode, digests=True)
             assert tuple(pw.shape) == (W.WIRES, S_, n, 4) and tuple(pi.shape) == (S_, n, 5, 4)
-            assert torch.equal(pw.view(-1), wires[:W.WIRES * S_ * n * 4]) and torch.equal(pi.view(-1), inp_t.view(-1))
+            assert torch.equal(pw.view(-1), wires.view(-1)) and torch.equal(pi.view(-1), inputs.view(-1))
             assert torch.equal(pd, ref_d)
 
 
@@ -180,28 +141,27 @@ def test_merkle_open_witness_against_model_and_perm_witness(torch_cuda, H, hades
         # the model, from the leaves alone
         lv = [S.from_mont(int_of(r)) for r in to_host(leaves).reshape(-1, 4)]
         pv = None if pad is None else [S.from_mont(int_of(r)) for r in to_host(pad).reshape(-1, 4)]
-        levels = W.merkle_levels(lv, arity, S.from_mont(tag), out_idx, pv, _perm_many(oracle))
+        levels = W.merkle_levels(lv, arity, S.from_mont(tag), out_idx, pv, perm_many_over(oracle))
         assert S.to_mont(levels[-1][0]) == int_of(to_host(tree[-1]))
         exp = W.merkle_path_inputs(levels, arity, S.from_mont(tag), idx_list, pv)
         got = to_host(inputs).reshape(depth, nq, 5, 4)
-        want = _mont_rows([v for step in exp for st in step for v in st]).reshape(depth, nq, 5, 4)
+        want = mont_rows([v for step in exp for st in step for v in st]).reshape(depth, nq, 5, 4)
         assert (got == want).all(), (n_leaves, arity)
         assert (got[:, 4:7] == 0).all()                               # out-of-range indices: all-zero states
         _path_checks(torch, wires, inputs, tree, torch.tensor(idx_list[:4] + [n_leaves] * 3 + [1], device="cuda"),
                      n_leaves, arity, out_idx, depth)
         # guard words and untouched inputs through the C entry point
-        guard_w, guard_i = _guarded(torch, W.WIRES * depth * nq), _guarded(torch, 5 * depth * nq)
+        guard_w, guard_i = Guarded(torch, (W.WIRES, depth * nq, 4)), Guarded(torch, (depth * nq, 20))
         bad = torch.zeros(1, dtype=torch.int32, device="cuda")
         leaves_before, tree_before = leaves.clone(), tree.clone()
         tg = (ctypes.c_uint64 * 4)(*limbs_of(tag))
         rc = hades_lib.hades252_merkle_open_witness_dev(leaves.data_ptr(), tree.data_ptr(), n_leaves, arity, tg,
                                                         None if pad is None else pad.data_ptr(), idx_t.data_ptr(), nq,
-                                                        guard_i.data_ptr(), guard_w.data_ptr(), bad.data_ptr(), None)
+                                                        guard_i.ptr, guard_w.ptr, bad.data_ptr(), None)
         assert rc == 0
-        torch.cuda.synchronize()
+        guard_i.check((n_leaves, arity))                              # guards whole, every word written (zero states too)
+        assert torch.equal(guard_w.check((n_leaves, arity)).view(-1), wires.view(-1))
         assert int(bad.item()) == 3
-        assert _guard_ok(guard_w, W.WIRES * depth * nq) and _guard_ok(guard_i, 5 * depth * nq)
-        assert torch.equal(guard_w[:W.WIRES * depth * nq * 4], wires.view(-1))
         assert torch.equal(leaves, leaves_before) and torch.equal(tree, tree_before)
 
 

@@ -16,44 +16,13 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import cipher_model as C  # noqa: E402
 import cipher_witness_model as CW  # noqa: E402
 from cipher_witness_model import P, S  # noqa: E402
-from gpu_common import to_dev, to_host  # noqa: E402
-from oracle_lib import limbs_of, int_of  # noqa: E402
+from gpu_common import (WIRES, Guarded, assert_wires_are_perm_witness, gadget_check, mont_rows, perm_many_over,  # noqa: E402
+                        to_dev, to_host)
+from oracle_lib import int_of  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-WIRES = 972
-GUARD = 0x5A5A5A5A5A5A5A5A
-NG = 64                                          # guard scalars (bytes for ok) behind every output buffer
-
-
-def _mont_rows(vals):
-    return np.array([limbs_of(S.to_mont(v)) for v in vals], dtype=np.uint64).reshape(-1, 4)
-
-
-def _perm_many(oracle):
-    """The model's perm_many over the C oracle (Montgomery limbs in between)."""
-    def run(states):
-        out = oracle.perm_batch(_mont_rows([v for st in states for v in st]).reshape(-1)).reshape(-1, 5, 4)
-        return [[S.from_mont(int_of(w)) for w in st] for st in out]
-    return run
-
-
-def _guarded(torch, n_scalars):
-    return torch.full(((n_scalars + NG) * 4,), GUARD, dtype=torch.int64, device="cuda")
-
-
-def _guard_ok(t, n_scalars):
-    return bool((t[n_scalars * 4:] == GUARD).all().item())
-
-
-def _gadget_check(wires_h, inputs_h, pairs):
-    for (s, i) in pairs:
-        st = [S.from_mont(int_of(inputs_h[s, i, w])) for w in range(5)]
-        spec = []
-        S.perm_gadget(st, spec)
-        got = [int_of(wires_h[g, s, i]) for g in range(WIRES)]
-        bad = [g for g in range(WIRES) if got[g] != S.to_mont(spec[g])]
-        assert not bad, ((s, i), bad[:8])
+NG = 64                                          # guard bytes behind ok (a byte per message: not Guarded's int64 rows)
 
 
 def _case(rng, n, m):
@@ -67,33 +36,27 @@ def _case(rng, n, m):
 
 def _run_encrypt(torch, hades_lib, dm, dk, dn, n, m, dom):
     S_ = CW.cipher_perms(m)
-    inputs, wires, ciphers = _guarded(torch, 5 * S_ * n), _guarded(torch, WIRES * S_ * n), _guarded(torch, n * (m + 1))
+    inputs, wires = Guarded(torch, (5 * S_ * n * 4,)), Guarded(torch, (WIRES * S_ * n * 4,))
+    ciphers = Guarded(torch, (n * (m + 1) * 4,))
     rc = hades_lib.hades252_cipher_encrypt_witness_dev(dm.data_ptr(), dk.data_ptr(), dn.data_ptr(), n, m, dom,
-                                                       inputs.data_ptr(), wires.data_ptr(), ciphers.data_ptr(), None)
+                                                       inputs.ptr, wires.ptr, ciphers.ptr, None)
     assert rc == 0
-    torch.cuda.synchronize()
-    assert _guard_ok(inputs, 5 * S_ * n) and _guard_ok(wires, WIRES * S_ * n) and _guard_ok(ciphers, n * (m + 1)), (n, m)
-    return inputs[:5 * S_ * n * 4], wires[:WIRES * S_ * n * 4], ciphers[:n * (m + 1) * 4]
+    return inputs.check((n, m)), wires.check((n, m)), ciphers.check((n, m))      # guards whole, every word written
 
 
 def _run_decrypt(torch, hades_lib, dc, dk, dn, n, m, dom, rej0=5):
     S_ = CW.cipher_perms(m)
-    inputs, wires, msgs = _guarded(torch, 5 * S_ * n), _guarded(torch, WIRES * S_ * n), _guarded(torch, n * m)
+    inputs, wires = Guarded(torch, (5 * S_ * n * 4,)), Guarded(torch, (WIRES * S_ * n * 4,))
+    msgs = Guarded(torch, (n * m * 4,))
     ok = torch.full((n + NG,), 0x77, dtype=torch.uint8, device="cuda")
     rej = torch.full((1,), rej0, dtype=torch.int32, device="cuda")          # the entry point ADDS to it
     rc = hades_lib.hades252_cipher_decrypt_witness_dev(dc.data_ptr(), dk.data_ptr(), dn.data_ptr(), n, m, dom,
-                                                       inputs.data_ptr(), wires.data_ptr(), msgs.data_ptr(), ok.data_ptr(),
-                                                       rej.data_ptr(), None)
+                                                       inputs.ptr, wires.ptr, msgs.ptr, ok.data_ptr(), rej.data_ptr(), None)
     assert rc == 0
-    torch.cuda.synchronize()
-    assert _guard_ok(inputs, 5 * S_ * n) and _guard_ok(wires, WIRES * S_ * n) and _guard_ok(msgs, n * m), (n, m)
+    # guards whole, every word written: a rejected lane's message too (zeroed, and zero is not the sentinel)
+    got = inputs.check((n, m)), wires.check((n, m)), msgs.check((n, m))
     assert bool((ok[n:] == 0x77).all())
-    return inputs[:5 * S_ * n * 4], wires[:WIRES * S_ * n * 4], msgs[:n * m * 4], ok[:n], int(rej.item()) - rej0
-
-
-def _defining_property(torch, H, inputs, wires, S_, n):
-    ref = H.perm_witness(inputs.view(S_ * n, 20))
-    assert torch.equal(wires.view(WIRES, S_ * n, 4), ref), n
+    return got + (ok[:n], int(rej.item()) - rej0)
 
 
 @pytest.mark.parametrize("m", [1, 2, 3, 4, 5, 8, 9])
@@ -106,25 +69,25 @@ def test_cipher_witness_against_model_and_perm_witness(torch_cuda, H, hades_lib,
         msgs, keys, nonces = _case(rng, n, m)
         dom_int = rng.choice([C.DOMAIN, rng.randrange(P)])
         dom = H._tag_arr(S.to_mont(dom_int))
-        hm = _mont_rows([v for x in msgs for v in x])
-        hk, hn = _mont_rows([v for k in keys for v in k]), _mont_rows(nonces)
+        hm = mont_rows([v for x in msgs for v in x])
+        hk, hn = mont_rows([v for k in keys for v in k]), mont_rows(nonces)
         dm, dk, dn = to_dev(torch, hm), to_dev(torch, hk), to_dev(torch, hn)
         # ---- encrypt ----
         e_in, e_wires, e_c = _run_encrypt(torch, hades_lib, dm, dk, dn, n, m, dom)
         assert (to_host(dm) == hm.reshape(-1)).all() and (to_host(dk) == hk.reshape(-1)).all()
         assert (to_host(dn) == hn.reshape(-1)).all()
-        exp_in, exp_c = CW.encrypt_inputs(msgs, keys, nonces, dom_int, _perm_many(oracle))
+        exp_in, exp_c = CW.encrypt_inputs(msgs, keys, nonces, dom_int, perm_many_over(oracle))
         got_in = to_host(e_in).reshape(S_, n, 5, 4)
-        assert (got_in == _mont_rows([v for step in exp_in for st in step for v in st]).reshape(S_, n, 5, 4)).all(), n
-        _defining_property(torch, H, e_in, e_wires, S_, n)
+        assert (got_in == mont_rows([v for step in exp_in for st in step for v in st]).reshape(S_, n, 5, 4)).all(), n
+        assert_wires_are_perm_witness(torch, H, e_in, e_wires)
         ref_c = torch.empty((n, m + 1, 4), dtype=torch.int64, device="cuda")
         assert hades_lib.hades252_cipher_encrypt_dev(dm.data_ptr(), dk.data_ptr(), dn.data_ptr(), n, m, dom,
                                                      ref_c.data_ptr(), None) == 0
         assert torch.equal(e_c.view(n, m + 1, 4), ref_c), n
-        assert (to_host(ref_c).reshape(n, m + 1, 4) == _mont_rows([v for c in exp_c for v in c]).reshape(n, m + 1, 4)).all()
+        assert (to_host(ref_c).reshape(n, m + 1, 4) == mont_rows([v for c in exp_c for v in c]).reshape(n, m + 1, 4)).all()
         wires_h = to_host(e_wires).reshape(WIRES, S_, n, 4)
         pairs = {(0, 0), (S_ - 1, n - 1), (rng.randrange(S_), rng.randrange(n))}
-        _gadget_check(wires_h, got_in, sorted(pairs))
+        gadget_check(wires_h, got_in, sorted(pairs))
         # ---- decrypt of the encryption: the same witness, the messages back ----
         c_before = ref_c.clone()
         d_in, d_wires, d_m, d_ok, d_rej = _run_decrypt(torch, hades_lib, ref_c, dk, dn, n, m, dom)
@@ -152,10 +115,10 @@ def test_decrypt_witness_tampered_and_non_canonical(torch_cuda, H, hades_lib, or
     S_ = CW.cipher_perms(m)
     rng = random.Random(n * 31 + m)
     msgs, keys, nonces = _case(rng, n, m)
-    hk, hn = _mont_rows([v for k in keys for v in k]), _mont_rows(nonces)
+    hk, hn = mont_rows([v for k in keys for v in k]), mont_rows(nonces)
     dk, dn = to_dev(torch, hk), to_dev(torch, hn)
     dom = H._tag_arr(H.CIPHER_DOMAIN)
-    c = to_host(H.cipher_encrypt(to_dev(torch, _mont_rows([v for x in msgs for v in x])), dk, dn, m)).reshape(n, m + 1, 4)
+    c = to_host(H.cipher_encrypt(to_dev(torch, mont_rows([v for x in msgs for v in x])), dk, dn, m)).reshape(n, m + 1, 4)
     c = c.copy()
     raw = [[int_of(w) for w in row] for row in c]                # the 256-bit words as stored
     kinds = ["tag", "word", "p", "2p", "max"]
@@ -187,17 +150,17 @@ def test_decrypt_witness_tampered_and_non_canonical(torch_cuda, H, hades_lib, or
     got_m = to_host(d_m).reshape(n, m, 4)
     assert (got_m[list(bad)] == 0).all()
     keep = want_ok == 1
-    assert (got_m[keep] == _mont_rows([v for x in msgs for v in x]).reshape(n, m, 4)[keep]).all()
+    assert (got_m[keep] == mont_rows([v for x in msgs for v in x]).reshape(n, m, 4)[keep]).all()
     # inputs: the model's, every word canonical.  The model takes a stored word w = mont(v) + k p as the integer v + k p: the
     # field element v, and not canonical when k > 0
     ints = [[S.from_mont(w % P) + (w // P) * P for w in row] for row in raw]
-    exp_in, exp_m, exp_ok = CW.decrypt_inputs(ints, keys, nonces, C.DOMAIN, _perm_many(oracle))
+    exp_in, exp_m, exp_ok = CW.decrypt_inputs(ints, keys, nonces, C.DOMAIN, perm_many_over(oracle))
     assert [int(x) for x in exp_ok] == want_ok.tolist()
     got_in = to_host(d_in).reshape(S_, n, 5, 4)
-    assert (got_in == _mont_rows([v for step in exp_in for st in step for v in st]).reshape(S_, n, 5, 4)).all()
+    assert (got_in == mont_rows([v for step in exp_in for st in step for v in st]).reshape(S_, n, 5, 4)).all()
     assert C.canonical(got_in).all()
-    _defining_property(torch, H, d_in, d_wires, S_, n)
-    _gadget_check(to_host(d_wires).reshape(WIRES, S_, n, 4), got_in, sorted({(S_ - 1, i) for i in list(bad)[:3]}))
+    assert_wires_are_perm_witness(torch, H, d_in, d_wires)
+    gadget_check(to_host(d_wires).reshape(WIRES, S_, n, 4), got_in, sorted({(S_ - 1, i) for i in list(bad)[:3]}))
     # side outputs are optional: NULL msgs / ok / counter write the same witness
     bare_in, bare_w = torch.empty_like(d_in), torch.empty_like(d_wires)
     assert hades_lib.hades252_cipher_decrypt_witness_dev(dc.data_ptr(), dk.data_ptr(), dn.data_ptr(), n, m, dom,

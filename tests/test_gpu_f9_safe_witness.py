@@ -22,12 +22,10 @@ import safe_model as M  # noqa: E402
 import safe_witness_model as W  # noqa: E402
 from safe_model import A, Q  # noqa: E402
 from safe_witness_model import P, S  # noqa: E402
-from gpu_common import CAP, TAG4, Guarded, to_dev, to_host  # noqa: E402
-from oracle_lib import int_of  # noqa: E402
+from gpu_common import CAP, TAG4, WIRES, Guarded, assert_wires_are_perm_witness, gadget_check, to_dev, to_host  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-WIRES = 972
 LAST_ROW = WIRES - 9                             # r2[0] of the last round; r2[j] = LAST_ROW + 2 j
 NS = (1, 63, 64, 65, 257)
 TAG = S.to_mont(0x5AFE)
@@ -47,16 +45,6 @@ def _edge_inputs(rng, n, k):
     return a
 
 
-def _gadget_check(wires_h, inputs_h, pairs):
-    for (s, i) in pairs:
-        st = [S.from_mont(int_of(inputs_h[s, i, w])) for w in range(5)]
-        spec = []
-        S.perm_gadget(st, spec)
-        got = [int_of(wires_h[g, s, i]) for g in range(WIRES)]
-        bad = [g for g in range(WIRES) if got[g] != S.to_mont(spec[g])]
-        assert not bad, ((s, i), bad[:8])
-
-
 def _one_shot(torch, hades_lib, H, d_in, n, pattern, tag_mont, with_out=True):
     """The raw call on guarded buffers -> (inputs [S * n, 5, 4], wires [972, S * n, 4], out [n, n_out, 4] or None)."""
     _, n_out, steps = H.safe_pattern(pattern)
@@ -68,11 +56,6 @@ def _one_shot(torch, hades_lib, H, d_in, n, pattern, tag_mont, with_out=True):
     assert rc == 0
     what = (n, _name(pattern))
     return inputs.check(what), wires.check(what), out.check(what) if with_out else None
-
-
-def _defining_property(torch, H, inputs, wires):
-    ref = H.perm_witness(inputs.reshape(-1, 20))
-    assert torch.equal(wires.reshape(WIRES, -1, 4), ref)
 
 
 @pytest.mark.parametrize("pattern", W.GPU_PATTERNS, ids=_name)
@@ -91,7 +74,7 @@ def test_one_shot_against_model_perm_witness_and_safe_hash(torch_cuda, H, hades_
         assert exp_in.shape == (steps, n, 5, 4)
         inputs_h = to_host(got_in).reshape(steps, n, 5, 4)
         assert (inputs_h == exp_in).all(), n
-        _defining_property(torch, H, got_in, got_wires)
+        assert_wires_are_perm_witness(torch, H, got_in, got_wires)
         ref_out = H.safe_hash(d_in, pattern, tag)
         assert torch.equal(got_out, ref_out), n
         assert (to_host(ref_out).reshape(n, n_out, 4) == exp_out).all(), n
@@ -104,7 +87,7 @@ def test_one_shot_against_model_perm_witness_and_safe_hash(torch_cuda, H, hades_
         assert torch.equal(bare_in, got_in) and torch.equal(bare_wires, got_wires), n
         wires_h = to_host(got_wires).reshape(WIRES, steps, n, 4)
         pairs = {(0, 0), (steps - 1, n - 1), (rng.randrange(steps), rng.randrange(n))}
-        _gadget_check(wires_h, inputs_h, sorted(pairs))
+        gadget_check(wires_h, inputs_h, sorted(pairs))
         if n == 65:                                       # the Python layer: same bytes in the documented shapes
             pw, pi, po = H.safe_witness(d_in.view(n, n_in, 4), pattern, tag)
             assert tuple(pw.shape) == (WIRES, steps, n, 4) and tuple(pi.shape) == (steps, n, 5, 4)
@@ -175,7 +158,7 @@ def test_every_cut_into_streaming_witness_calls_equals_the_one_shot_bytes(torch_
     d_in = to_dev(torch, h_in).view(n, n_in, 4)
     want_in, want_wires, want_out = _one_shot(torch, hades_lib, H, d_in, n, pattern, TAG)
     assert (to_host(want_in).reshape(steps, n, 5, 4) == W.batch_inputs(pattern, h_in, TAG, oracle.perm_batch)[0]).all()
-    _defining_property(torch, H, want_in, want_wires)
+    assert_wires_are_perm_witness(torch, H, want_in, want_wires)
     agg = M.aggregate(pattern)
     ways = 0
     for pieces in itertools.product(*[list(W.cuts(k)) for _, k in agg]):

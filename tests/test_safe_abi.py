@@ -5,25 +5,18 @@ Python SafeSponge refuses departures from its pattern; the C++ wrappers compile 
 k_safe_lanes in the built library has no scratch and fits its launch bounds; and the new sources leave the key of the
 committed secondary-kernel counter record alone."""
 import ctypes
-import os
 import random
-import re
-import subprocess
 
 import pytest
 
+import abi_common
+import codeobj
 import safe_model as M
+from abi_common import INVALID, MIS, PTR, limbs4
 from safe_model import A, Q
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "hades252_amd", "csrc")
 SYMS = ["hades252_safe_pattern", "hades252_safe_hash_dev", "hades252_safe_absorb_dev", "hades252_safe_squeeze_dev",
         "hades252_safe_hash"]
-INVALID = -1
-
-# fake, never dereferenced: every call below must be refused by the argument checks
-PTR = 0x10000          # 16-byte aligned
-MIS = PTR + 8          # misaligned
 
 INVALID_PATTERNS = {
     "empty": [],
@@ -46,19 +39,10 @@ def _calls(pattern):
     return (ctypes.c_uint32 * max(len(words), 1))(*words), len(words)
 
 
-def _tag():
-    return (ctypes.c_uint64 * 4)(1, 2, 3, 4)
-
-
 def test_symbols_are_declared_bound_and_exported(hades_lib):
     from hades252_amd import _lib
-    header = open(os.path.join(ROOT, "include", "hades252.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for s in SYMS:
-        assert re.search(r"\b%s\s*\(" % s, text), s
-        assert s in _lib.SIGNATURES, s
-        assert hasattr(raw, s), s
+    abi_common.assert_declared_bound_exported(SYMS)
+    header = abi_common.header()
     for line, value in (("#define HADES252_SAFE_MAX_CALLS 64", _lib.SAFE_MAX_CALLS),
                         ("#define HADES252_SAFE_MAX_WORDS 1048576", _lib.SAFE_MAX_WORDS),
                         ("#define HADES252_SAFE_ABSORB 2147483648u", _lib.SAFE_ABSORB)):
@@ -67,10 +51,9 @@ def test_symbols_are_declared_bound_and_exported(hades_lib):
 
 
 def test_header_says_convention_unpinned():
-    text = open(os.path.join(ROOT, "include", "hades252.h")).read()
-    block = text[text.index("batched duplex sponge"):text.index("#define HADES252_SAFE_MAX_CALLS")]
-    assert "CONVENTION UNPINNED" in block and "recalled from dusk-safe" in block and "tests/safe_model.py" in block
-    assert "1 025 .. 16 384" in block                          # says which sizes have no form of their own
+    abi_common.header_block("batched duplex sponge", "#define HADES252_SAFE_MAX_CALLS",
+                            ("CONVENTION UNPINNED", "recalled from dusk-safe", "tests/safe_model.py",
+                             "1 025 .. 16 384"))                # says which sizes have no form of their own
 
 
 def test_pattern_against_the_model(hades_lib):
@@ -99,8 +82,8 @@ def test_every_class_of_invalid_pattern_is_refused_everywhere(hades_lib, what):
     arr, k = _calls(pat)
     n_in = ctypes.c_size_t(7)
     assert hades_lib.hades252_safe_pattern(arr, k, ctypes.byref(n_in), None, None) == INVALID and n_in.value == 7
-    assert hades_lib.hades252_safe_hash_dev(PTR, 5, arr, k, _tag(), PTR, None) == INVALID
-    assert hades_lib.hades252_safe_hash(PTR, 5, arr, k, _tag(), PTR) == INVALID
+    assert hades_lib.hades252_safe_hash_dev(PTR, 5, arr, k, limbs4(), PTR, None) == INVALID
+    assert hades_lib.hades252_safe_hash(PTR, 5, arr, k, limbs4(), PTR) == INVALID
     from hades252_amd import strategy as H
     with pytest.raises(ValueError):
         H.safe_pattern(pat)
@@ -112,7 +95,7 @@ def test_one_shot_argument_rules(hades_lib):
     arr, k = _calls([A(3), Q(2)])
     dev, host = hades_lib.hades252_safe_hash_dev, hades_lib.hades252_safe_hash
 
-    def d(inp=PTR, n=5, calls=arr, n_calls=k, tag=_tag(), out=PTR):
+    def d(inp=PTR, n=5, calls=arr, n_calls=k, tag=limbs4(), out=PTR):
         return dev(inp, n, calls, n_calls, tag, out, None)
 
     assert d(inp=None, n=0, calls=None, n_calls=0, tag=None, out=None) == 0      # n = 0: a no-op success, whatever else
@@ -121,11 +104,11 @@ def test_one_shot_argument_rules(hades_lib):
                {"out": MIS}, {"n": (1 << 30) + 1}):
         assert d(**kw) == INVALID, kw
     assert hades_lib.hades252_safe_pattern(None, 2, None, None, None) == INVALID
-    for args in ((None, 3, arr, k, _tag(), PTR), (PTR, 3, None, k, _tag(), PTR), (PTR, 3, arr, k, None, PTR),
-                 (PTR, 3, arr, k, _tag(), None), (PTR, 3, arr, 0, _tag(), PTR)):
+    for args in ((None, 3, arr, k, limbs4(), PTR), (PTR, 3, None, k, limbs4(), PTR), (PTR, 3, arr, k, None, PTR),
+                 (PTR, 3, arr, k, limbs4(), None), (PTR, 3, arr, 0, limbs4(), PTR)):
         assert host(*args) == INVALID
     too_many = (2**64 - 1) // (5 * 32) + 1                       # n x (n_in + n_out) x 32 bytes would not fit size_t
-    assert host(PTR, too_many, arr, k, _tag(), PTR) == INVALID
+    assert host(PTR, too_many, arr, k, limbs4(), PTR) == INVALID
 
 
 def test_streaming_argument_rules_leave_the_cursor_alone(hades_lib):
@@ -202,8 +185,7 @@ def test_python_layer_checks_shapes():
 
 
 def test_cpp_wrappers_compile_and_link(hades_lib, tmp_path):
-    src = tmp_path / "safe.cpp"
-    src.write_text(r'''
+    abi_common.compile_and_run(tmp_path, "safe", r'''
 #include "hades252.hpp"
 #include <cstdio>
 #include <vector>
@@ -229,66 +211,27 @@ int main() {
     }
     return 0;
 }
-''')
-    exe = tmp_path / "safe"
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-L", CSRC,
-                    "-lhades252", "-Wl,-rpath," + CSRC, "-o", str(exe)], check=True)
-    assert exe.exists()
+''', run=False)       # it would touch a device: link only
 
 
-LLVM = os.environ.get("ROCM_LLVM_BIN", "/opt/rocm/llvm/bin")
-
-
-@pytest.fixture(scope="module")
-def safe_resources(hades_lib, tmp_path_factory):
-    """The resource metadata of the duplex sponge's kernels, read from the gfx950 code object INSIDE the built library (no
-    second compile: the code object of libhades252.so is unbundled and its AMDGPU metadata note read)."""
-    tools = [os.path.join(LLVM, t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")]
-    if not all(os.path.exists(t) for t in tools):
-        pytest.skip("ROCm LLVM tools not available")
-    objcopy, bundler, readelf = tools
-    from hades252_amd import _lib
-    tmp_path = tmp_path_factory.mktemp("codeobj")
-    fat, co = tmp_path / "fatbin", tmp_path / "gfx950.co"
-    subprocess.run([objcopy, "--dump-section", ".hip_fatbin=%s" % fat, _lib.LIB_PATH, str(tmp_path / "scratch.so")],
-                   check=True)
-    subprocess.run([bundler, "--unbundle", "--type=o", "--input=%s" % fat, "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-                    "--output=%s" % co], check=True)
-    notes = subprocess.run([readelf, "--notes", str(co)], check=True, capture_output=True, text=True).stdout
-    res = {}
-    for entry in re.split(r"^  - (?=\.)", notes, flags=re.M)[1:]:          # one entry of amdhsa.kernels per kernel
-        m = re.search(r"^    \.name:\s+(\S+)", entry, re.M)
-        if m is None or "k_safe" not in m.group(1):
-            continue
-        res[m.group(1)] = {k: int(v) for k, v in re.findall(r"^\s*\.(\w+):\s+(\d+)$", entry, re.M)
-                           if k in ("agpr_count", "vgpr_count", "vgpr_spill_count", "sgpr_spill_count",
-                                    "private_segment_fixed_size", "kernarg_segment_size")}
-    return res
-
-
-def test_safe_kernels_have_no_scratch_and_fit_their_bounds(safe_resources):
-    lane = [k for k in safe_resources if "k_safe_lanes" not in k]
-    wave = [k for k in safe_resources if "k_safe_lanes" in k]
-    assert len(lane) == 1 and len(wave) == 2, sorted(safe_resources)
-    for name, r in safe_resources.items():
+def test_safe_kernels_have_no_scratch_and_fit_their_bounds(hades_lib):
+    co = codeobj.load()
+    lane, wave = co.kernels("k_safe"), co.kernels("k_safe_lanes")
+    assert len(lane) == 1 and len(wave) == 2, sorted(co.meta)
+    for name in lane + wave:
+        r = co.meta[name]
         assert r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0, (name, r)
         assert r["kernarg_segment_size"] >= 256                # the aggregated calls travel by value in the arguments
     for name in lane:         # __launch_bounds__(256, 3): 3 waves per SIMD -> at most 168 VGPRs (+ AGPRs: one file)
-        r = safe_resources[name]
+        r = co.meta[name]
         assert r["vgpr_count"] + r["agpr_count"] <= 168, (name, r)
     for name in wave:         # __launch_bounds__(256): 1 wave per SIMD admits 512, the lanes arithmetic needs <= 128
-        r = safe_resources[name]
+        r = co.meta[name]
         assert r["vgpr_count"] + r["agpr_count"] <= 128, (name, r)
 
 
 def test_counter_record_of_the_secondary_kernels_stays_keyed():
     """The duplex sponge's sources stay out of build.device_source_hash (they define and launch none of the kernels of the
     committed `secondary_kernels` counter record), so adding them leaves that record valid for bench.py."""
-    import json
-    from hades252_amd import build
-    new = {"kernels_safe.hpp", "abi_safe.hpp"}
-    assert new <= set(build.UNRECORDED_KERNEL_DEPS) and new | {"host_safe.hpp"} <= set(build.DEPS)
-    assert not (new | {"host_safe.hpp", "kernels_cipher.hpp"}) & set(build.DEVICE_DEPS + build.LAUNCH_POLICY_DEPS)
-    with open(os.path.join(ROOT, "profiles", "hbm_traffic.json")) as f:
-        sec = json.load(f)["secondary_kernels"]
-    assert sec["device_source_hash"] == build.device_source_hash()
+    abi_common.assert_outside_counter_records(["kernels_safe.hpp", "abi_safe.hpp"],
+                                              also_in_deps=["host_safe.hpp", "kernels_cipher.hpp"])

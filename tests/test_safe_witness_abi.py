@@ -4,24 +4,16 @@ before the device is touched and leaves *cursor and *step alone; the Python laye
 link; the new code leaves the keys of the committed counter records alone; and the code object of k_witness_duplex in the
 built library has k_perm_witness's budget."""
 import ctypes
-import json
-import os
-import re
-import subprocess
 
 import pytest
 
+import abi_common
+import codeobj
 import safe_model as M
+from abi_common import INVALID, MIS, PTR, limbs4
 from safe_model import A, Q
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "hades252_amd", "csrc")
 SYMS = ["hades252_safe_witness_dev", "hades252_safe_absorb_witness_dev", "hades252_safe_squeeze_witness_dev"]
-INVALID = -1
-
-# fake, never dereferenced: every call below must be refused by the argument checks (or be a no-op success)
-PTR = 0x10000          # 16-byte aligned
-MIS = PTR + 8          # misaligned
 
 
 def _calls(pattern):
@@ -29,28 +21,17 @@ def _calls(pattern):
     return (ctypes.c_uint32 * max(len(words), 1))(*words), len(words)
 
 
-def _tag():
-    return (ctypes.c_uint64 * 4)(1, 2, 3, 4)
-
-
 def test_symbols_are_declared_bound_and_exported(hades_lib):
-    from hades252_amd import _lib
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hades252.h")).read(), flags=re.S)
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for s in SYMS:
-        assert re.search(r"\b%s\s*\(" % s, text), s
-        assert s in _lib.SIGNATURES, s
-        assert hasattr(raw, s), s
+    abi_common.assert_declared_bound_exported(SYMS)
 
 
 def test_header_states_the_contract():
-    text = open(os.path.join(ROOT, "include", "hades252.h")).read()
+    abi_common.header_block("gadget witnesses of the duplex sponge", "int hades252_safe_witness_dev",
+                            ("CONVENTION UNPINNED", "rec = s * n", "hades252_perm_witness_dev(inputs) byte for byte", "2^30",
+                             "may be NULL", "*step + q <= total_steps", "on success only", "read, not changed",
+                             "no one-per-wave latency form"))
+    text = abi_common.header()
     start = text.index("gadget witnesses of the duplex sponge")
-    block = text[start:text.index("int hades252_safe_witness_dev")]
-    for needle in ("CONVENTION UNPINNED", "rec = s * n", "hades252_perm_witness_dev(inputs) byte for byte", "2^30",
-                   "may be NULL", "*step + q <= total_steps", "on success only", "read, not changed",
-                   "no one-per-wave latency form"):
-        assert needle in block, needle
     # after the cipher-witness section, which follows the plain duplex sponge
     assert text.index("batched duplex sponge") < text.index("gadget witnesses of the cipher") < start
     assert text.index("int hades252_cipher_decrypt_witness_dev(") < start
@@ -59,7 +40,7 @@ def test_header_states_the_contract():
 def test_one_shot_argument_rules(hades_lib):
     f = hades_lib.hades252_safe_witness_dev
     arr, k = _calls([A(3), Q(2), A(2), Q(1)])                      # S = 2
-    tag = _tag()
+    tag = limbs4()
 
     def call(d_in=PTR, n=5, calls=arr, n_calls=k, t=tag, inp=PTR, wires=PTR, out=None):
         return f(d_in, n, calls, n_calls, t, inp, wires, out, None)
@@ -121,8 +102,7 @@ def test_python_layer_checks_types_and_patterns():
 
 
 def test_cpp_wrappers_compile_and_link(hades_lib, tmp_path):
-    src = tmp_path / "safe_witness.cpp"
-    src.write_text(r'''
+    out = abi_common.compile_and_run(tmp_path, "safe_witness", r'''
 #include "hades252.hpp"
 #include <cstdio>
 int main() {
@@ -150,69 +130,17 @@ int main() {
     return 0;
 }
 ''')
-    exe = tmp_path / "safe_witness"
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-L", CSRC,
-                    "-lhades252", "-Wl,-rpath," + CSRC, "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines()
     assert out[0] == "1" and out[-1] == "0 0" and len(out) == 5, out
 
 
 def test_counter_records_stay_keyed():
     """The duplex sponge witness lives in kernels_witness.hpp / abi_witness.hpp, outside build.device_source_hash and
     perm_fast_hash, so bench.py keeps replaying its counter-backed traffic."""
-    from hades252_amd import build
-    new = {"kernels_witness.hpp", "abi_witness.hpp"}
-    assert new <= set(build.UNRECORDED_KERNEL_DEPS) and new <= set(build.DEPS)
-    assert not new & set(build.DEVICE_DEPS + build.LAUNCH_POLICY_DEPS + build.PERM_FAST_DEPS)
-    with open(os.path.join(ROOT, "profiles", "hbm_traffic.json")) as f:
-        rec = json.load(f)
-    assert rec["secondary_kernels"]["device_source_hash"] == build.device_source_hash()
-    assert json.dumps(rec).count(build.perm_fast_hash()) >= 1
+    abi_common.assert_outside_counter_records(["kernels_witness.hpp", "abi_witness.hpp"])
 
 
-LLVM = os.environ.get("ROCM_LLVM_BIN", "/opt/rocm/llvm/bin")
-
-
-@pytest.fixture(scope="module")
-def code_object(hades_lib, tmp_path_factory):
-    """(resource metadata, disassembly) of the witness kernels, read from the gfx950 code object INSIDE the built library."""
-    tools = [os.path.join(LLVM, t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf", "llvm-objdump")]
-    if not all(os.path.exists(t) for t in tools):
-        pytest.skip("ROCm LLVM tools not available")
-    objcopy, bundler, readelf, objdump = tools
-    from hades252_amd import _lib
-    tmp_path = tmp_path_factory.mktemp("codeobj")
-    fat, co = tmp_path / "fatbin", tmp_path / "gfx950.co"
-    subprocess.run([objcopy, "--dump-section", ".hip_fatbin=%s" % fat, _lib.LIB_PATH, str(tmp_path / "scratch.so")],
-                   check=True)
-    subprocess.run([bundler, "--unbundle", "--type=o", "--input=%s" % fat, "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-                    "--output=%s" % co], check=True)
-    notes = subprocess.run([readelf, "--notes", str(co)], check=True, capture_output=True, text=True).stdout
-    res = {}
-    for entry in re.split(r"^  - (?=\.)", notes, flags=re.M)[1:]:
-        m = re.search(r"^    \.name:\s+(\S+)", entry, re.M)
-        if m is None or "witness" not in m.group(1):
-            continue
-        res[m.group(1)] = {k: int(v) for k, v in re.findall(r"^\s*\.(\w+):\s+(\d+)$", entry, re.M)
-                           if k in ("agpr_count", "vgpr_count", "vgpr_spill_count", "sgpr_spill_count",
-                                    "private_segment_fixed_size", "group_segment_fixed_size")}
-    text = subprocess.run([objdump, "-d", str(co)], check=True, capture_output=True, text=True).stdout
-    parts = re.split(r"^[0-9a-f]+ <(\S+)>:$", text, flags=re.M)
-    bodies = {parts[i]: parts[i + 1] for i in range(1, len(parts), 2) if "witness" in parts[i]}
-    return res, bodies
-
-
-def test_duplex_witness_kernel_has_the_perm_witness_budget(code_object):
-    res, bodies = code_object
-    (perm,) = [k for k in bodies if "k_perm_witness" in k]
-    (name,) = [k for k in bodies if "k_witness_duplex" in k]     # one kernel: one-shot and streaming
-    for other in ("k_safe", "k_cipher", "k_witness_sponge", "k_witness_cipher", "k_perm_witness"):
-        assert other not in name                                 # the neighbours' tests count kernels by these substrings
-    ref = len(re.findall(r"\bv_mad_[iu]64_[iu]32\b", bodies[perm]))
-    mads = len(re.findall(r"\bv_mad_[iu]64_[iu]32\b", bodies[name]))
-    assert abs(mads - ref) <= 0.02 * ref, (name, mads, ref)      # ONE call site of the round loop
-    assert "scratch_" not in bodies[name]
-    r = res[name]
-    print(name, r, "v_mad", mads, "against", ref)
-    assert r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0, (name, r)
-    assert r["vgpr_count"] + r["agpr_count"] <= 152 and r["sgpr_spill_count"] <= 8, (name, r)
+def test_duplex_witness_kernel_has_the_perm_witness_budget(hades_lib):
+    co = codeobj.load()
+    (name,) = co.kernels("k_witness_duplex")                     # one kernel: one-shot and streaming
+    print(name, co.meta[name], "v_mad", codeobj.mads(co.body(name)))
+    codeobj.assert_perm_witness_budget(co, [name])

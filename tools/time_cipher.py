@@ -15,18 +15,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 from hades252_amd import strategy as H, _lib  # noqa: E402
-
-
-def timed(fn, reps):
-    fn()                                               # warm-up (code object, first touch of the buffers)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps / 1e3            # seconds per call
+from timing import timed  # noqa: E402
 
 
 def main():

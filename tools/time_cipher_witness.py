@@ -16,21 +16,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 from hades252_amd import strategy as H, _lib  # noqa: E402
-
-WIRES = 972
-
-
-def timed(fn, reps):
-    fn()                                               # warm-up (code object, first touch of the buffers)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps / 1e3            # seconds per call
-
+from timing import WIRES, perm_witness_rate, report, timed  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
@@ -41,26 +27,11 @@ def main():
     dom = H._tag_arr(H.CIPHER_DOMAIN)
     out = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "rows": []}
 
-    def perm_witness_rate(n_perms, wires):
-        states = H.gen_b(5 * n_perms, dev, first_elem=3)
-        t = timed(lambda: _lib.check(lib.hades252_perm_witness_dev(states.data_ptr(), wires.data_ptr(), n_perms, stream()),
-                                     "perm_witness"), args.reps)
-        del states
-        out["rows"].append({"op": "perm_witness", "perms": n_perms, "ms": t * 1e3, "perms_per_s": n_perms / t})
-        print("perm_witness       perms=%-8d %9.3f ms  %7.1f M perms/s" % (n_perms, t * 1e3, n_perms / t / 1e6), flush=True)
-        return n_perms / t
-
-    def report(op, n_perms, t, ref_rate, extra=""):
-        row = {"op": op, "perms": n_perms, "ms": t * 1e3, "perms_per_s": n_perms / t, "vs_perm_witness": n_perms / t / ref_rate}
-        out["rows"].append(row)
-        print("%-18s perms=%-8d %9.3f ms  %7.1f M perms/s  (%.3f x perm_witness)%s"
-              % (op, n_perms, t * 1e3, n_perms / t / 1e6, row["vs_perm_witness"], extra), flush=True)
-
     for n, m in ((1 << 19, 2), (1 << 18, 5)):
         S = H.cipher_perms(m)
         n_perms = S * n
         wires = torch.empty((WIRES, n_perms, 4), dtype=torch.int64, device=dev)
-        ref = perm_witness_rate(n_perms, wires)
+        ref = perm_witness_rate(out["rows"], n_perms, wires, args.reps)
         msgs = H.gen_b(n * m, dev, first_elem=1 << 30)
         keys = H.gen_b(2 * n, dev, first_elem=1 << 31)
         nonces = H.gen_b(n, dev, first_elem=1 << 32)
@@ -69,14 +40,14 @@ def main():
         t = timed(lambda: _lib.check(lib.hades252_cipher_encrypt_witness_dev(
             msgs.data_ptr(), keys.data_ptr(), nonces.data_ptr(), n, m, dom, inputs.data_ptr(), wires.data_ptr(),
             ciphers.data_ptr(), stream()), "cipher_encrypt_witness"), args.reps)
-        report("encrypt_witness", n_perms, t, ref, "  n=%d M=%d" % (n, m))
+        report(out["rows"], "encrypt_witness", n_perms, t, ref, "  n=%d M=%d" % (n, m))
         back = torch.empty((n, m, 4), dtype=torch.int64, device=dev)
         ok = torch.empty(n, dtype=torch.uint8, device=dev)
         rej = torch.zeros(1, dtype=torch.int32, device=dev)
         t = timed(lambda: _lib.check(lib.hades252_cipher_decrypt_witness_dev(
             ciphers.data_ptr(), keys.data_ptr(), nonces.data_ptr(), n, m, dom, inputs.data_ptr(), wires.data_ptr(),
             back.data_ptr(), ok.data_ptr(), rej.data_ptr(), stream()), "cipher_decrypt_witness"), args.reps)
-        report("decrypt_witness", n_perms, t, ref, "  n=%d M=%d" % (n, m))
+        report(out["rows"], "decrypt_witness", n_perms, t, ref, "  n=%d M=%d" % (n, m))
         assert int(rej.item()) == 0 and torch.equal(back, msgs.view(n, m, 4))
         del wires, msgs, keys, nonces, inputs, ciphers, back, ok, rej
 

@@ -18,8 +18,8 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 from hades252_amd import strategy as H, _lib  # noqa: E402
+from timing import WIRES, perm_witness_rate, timed, witness_line  # noqa: E402
 
-WIRES = 972
 A = lambda n: ("absorb", n)      # noqa: E731
 Q = lambda n: ("squeeze", n)     # noqa: E731
 TARGET = 0.9
@@ -27,18 +27,6 @@ TARGET = 0.9
 
 def name(pattern):
     return "[" + ",".join("%s%d" % ("A" if kind == "absorb" else "S", n) for kind, n in pattern) + "]"
-
-
-def timed(fn, reps):
-    fn()                                               # warm-up (code object, first touch of the buffers)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps / 1e3            # seconds per call
 
 
 def main():
@@ -53,13 +41,7 @@ def main():
     n_perms = 1 << 20
     wires = torch.empty((WIRES, n_perms, 4), dtype=torch.int64, device=dev)
     inputs = torch.empty((n_perms, 5, 4), dtype=torch.int64, device=dev)
-    states = H.gen_b(5 * n_perms, dev, first_elem=3)
-    t = timed(lambda: _lib.check(lib.hades252_perm_witness_dev(states.data_ptr(), wires.data_ptr(), n_perms, stream()),
-                                 "perm_witness"), args.reps)
-    del states
-    ref = n_perms / t
-    out["rows"].append({"op": "perm_witness", "perms": n_perms, "ms": t * 1e3, "perms_per_s": ref})
-    print("%-34s perms=%-8d %9.3f ms  %7.1f M perms/s" % ("perm_witness", n_perms, t * 1e3, ref / 1e6), flush=True)
+    ref = perm_witness_rate(out["rows"], n_perms, wires, args.reps, width=34)
 
     for pattern, n, targeted in (([A(4), Q(1)], 1 << 20, True), ([A(3), Q(2), A(2), Q(1)], 1 << 19, True),
                                  ([A(1), Q(8)], 1 << 19, True), ([A(1), Q(64)], 1 << 16, False)):
@@ -77,8 +59,8 @@ def main():
         if targeted:
             row["meets_target"] = ratio >= TARGET
         out["rows"].append(row)
-        print("%-34s perms=%-8d %9.3f ms  %7.1f M perms/s  (%.3f x perm_witness%s)"
-              % ("safe_witness %s x 2^%d" % (name(pattern), n.bit_length() - 1), n_perms, t * 1e3, n_perms / t / 1e6, ratio,
+        print("%s  (%.3f x perm_witness%s)"
+              % (witness_line("safe_witness %s x 2^%d" % (name(pattern), n.bit_length() - 1), n_perms, t, width=34), ratio,
                  ", target %.1f: %s" % (TARGET, "met" if ratio >= TARGET else "MISSED") if targeted else ", no target"),
               flush=True)
         del d_in, d_out

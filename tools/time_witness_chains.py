@@ -16,25 +16,13 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 from hades252_amd import strategy as H, _lib  # noqa: E402
+from timing import WIRES, perm_witness_rate, report, timed  # noqa: E402
 
-WIRES = 972
 P = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
 
 
 def mont(v):
     return v * (1 << 256) % P
-
-
-def timed(fn, reps):
-    fn()                                               # warm-up (code object, first touch of the buffers)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps / 1e3            # seconds per call
 
 
 def main():
@@ -46,33 +34,17 @@ def main():
     cap = H._tag_arr(mont(1 << 64))                    # the "sponge/pad10" capacity of include/hades252.h
     out = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "rows": []}
 
-    def perm_witness_rate(n_perms, wires):
-        states = H.gen_b(5 * n_perms, dev, first_elem=3)
-        t = timed(lambda: _lib.check(lib.hades252_perm_witness_dev(states.data_ptr(), wires.data_ptr(), n_perms, stream()),
-                                     "perm_witness"), args.reps)
-        del states
-        row = {"op": "perm_witness", "perms": n_perms, "ms": t * 1e3, "perms_per_s": n_perms / t}
-        out["rows"].append(row)
-        print("perm_witness       perms=%-8d %9.3f ms  %7.1f M perms/s" % (n_perms, t * 1e3, n_perms / t / 1e6), flush=True)
-        return n_perms / t
-
-    def report(op, n_perms, t, ref_rate, extra=""):
-        row = {"op": op, "perms": n_perms, "ms": t * 1e3, "perms_per_s": n_perms / t, "vs_perm_witness": n_perms / t / ref_rate}
-        out["rows"].append(row)
-        print("%-18s perms=%-8d %9.3f ms  %7.1f M perms/s  (%.3f x perm_witness)%s"
-              % (op, n_perms, t * 1e3, n_perms / t / 1e6, row["vs_perm_witness"], extra), flush=True)
-
     # ---- sponge: 2^19 messages x 2 blocks ----
     n, msg_len = 1 << 19, 7
     n_perms = 2 * n
     wires = torch.empty((WIRES, n_perms, 4), dtype=torch.int64, device=dev)
-    ref = perm_witness_rate(n_perms, wires)
+    ref = perm_witness_rate(out["rows"], n_perms, wires, args.reps)
     msgs = H.gen_b(n * msg_len, dev, first_elem=1 << 30)
     inputs = torch.empty((n_perms, 5, 4), dtype=torch.int64, device=dev)
     t = timed(lambda: _lib.check(lib.hades252_sponge_witness_dev(msgs.data_ptr(), n, msg_len, cap, 1, inputs.data_ptr(),
                                                                  wires.data_ptr(), None, stream()), "sponge_witness"),
               args.reps)
-    report("sponge_witness", n_perms, t, ref, "  n=%d msg_len=%d" % (n, msg_len))
+    report(out["rows"], "sponge_witness", n_perms, t, ref, "  n=%d msg_len=%d" % (n, msg_len))
     del msgs, inputs, wires
 
     # ---- Merkle: depth 10 (2^20 leaves, arity 4) x 2^17 queries ----
@@ -83,7 +55,7 @@ def main():
     depth = H.merkle_depth(n_leaves, arity)
     n_perms = depth * nq
     wires = torch.empty((WIRES, n_perms, 4), dtype=torch.int64, device=dev)
-    ref = perm_witness_rate(n_perms, wires)
+    ref = perm_witness_rate(out["rows"], n_perms, wires, args.reps)
     idx = torch.randint(0, n_leaves, (nq,), device=dev, generator=torch.Generator(device=dev).manual_seed(1))
     inputs = torch.empty((n_perms, 5, 4), dtype=torch.int64, device=dev)
     tg = H._tag_arr(tag_mont)
@@ -91,7 +63,7 @@ def main():
                                                                       None, idx.data_ptr(), nq, inputs.data_ptr(),
                                                                       wires.data_ptr(), None, stream()),
                                  "merkle_open_witness"), args.reps)
-    report("merkle_witness", n_perms, t, ref, "  depth=%d queries=%d" % (depth, nq))
+    report(out["rows"], "merkle_witness", n_perms, t, ref, "  depth=%d queries=%d" % (depth, nq))
     del leaves, tree, wires, inputs
 
     # ---- one two-block message per call ----
