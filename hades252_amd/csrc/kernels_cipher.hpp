@@ -53,14 +53,15 @@ __device__ __forceinline__ void cipher_gather(const uint8_t *base, size_t stride
                                               uint8_t *slab, Fr (&w)[4], int lo = 0) {
     constexpr int kRec = lds_rec_bytes(4);
     const int lane = threadIdx.x & (kWave - 1), part = lane & 7, j = part >> 1;
-    // message 8k + lane / 8: one per-lane address, a wave-uniform step of 8 messages
-    const uint8_t *p = base + ((rec0 + (lane >> 3)) * stride + first + j - lo) * 32 + (part & 1) * 16;
+    // message 8k + lane / 8: one per-lane offset, a wave-uniform step of 8 messages.  (An offset, not a pointer: for a slot
+    // j < lo it wraps to before the message -- never read -- and C++ does not allow such a pointer even to be formed.)
+    const size_t off = ((rec0 + (lane >> 3)) * stride + first + j - lo) * 32 + (part & 1) * 16;
     const size_t step = 8 * stride * 32;
 #pragma unroll
     for (int k = 0; k < 8; k++) {
         const int m = 8 * k + (lane >> 3);
         uint4 v = make_uint4(0, 0, 0, 0);
-        if (j >= lo && j < lo + cnt && rec0 + m < n) v = *reinterpret_cast<const uint4 *>(p + k * step);
+        if (j >= lo && j < lo + cnt && rec0 + m < n) v = *reinterpret_cast<const uint4 *>(base + off + k * step);
         *reinterpret_cast<uint4 *>(slab + m * kRec + part * 16) = v;
     }
     wave_lds_fence();
@@ -88,7 +89,7 @@ __device__ __forceinline__ void cipher_scatter(uint8_t *base, size_t stride, siz
         wave_lds_fence();
     }
     const uint64_t bad_mask = ZERO_BAD ? __ballot(bad) : 0;
-    uint8_t *p = base + ((rec0 + (lane >> 3)) * stride + first + j - lo) * 32 + (part & 1) * 16;
+    const size_t off = ((rec0 + (lane >> 3)) * stride + first + j - lo) * 32 + (part & 1) * 16;   // (see cipher_gather)
     const size_t step = 8 * stride * 32;
 #pragma unroll
     for (int k = 0; k < 8; k++) {
@@ -96,7 +97,7 @@ __device__ __forceinline__ void cipher_scatter(uint8_t *base, size_t stride, siz
         uint4 v = make_uint4(0, 0, 0, 0);
         if constexpr (!ZERO_BAD) v = *reinterpret_cast<const uint4 *>(slab + m * kRec + part * 16);
         const bool go = ZERO_BAD ? ((bad_mask >> m) & 1) != 0 : true;
-        if (go && j >= lo && j < lo + cnt && rec0 + m < n) *reinterpret_cast<uint4 *>(p + k * step) = v;
+        if (go && j >= lo && j < lo + cnt && rec0 + m < n) *reinterpret_cast<uint4 *>(base + off + k * step) = v;
     }
     if constexpr (!ZERO_BAD) wave_lds_fence();
 }

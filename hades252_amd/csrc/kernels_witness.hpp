@@ -407,8 +407,8 @@ __global__ void __launch_bounds__(kBlock, 3) k_witness_duplex(const uint8_t *__r
         safe_permuted(parked_calls, k.n_calls, slot.walk);     // (after the last permutation the walk is not read again)
         parked_slot[wave + z] = slot;
         const bool last = t == n_perms;
-        uint8_t *dst = last ? k.states + (size_t)i * 160 : inputs + rec * 160;
-        if (live && !(last && k.states == nullptr)) {
+        if (live && !(last && k.states == nullptr)) {       // (no pointer is formed from a NULL k.states)
+            uint8_t *dst = last ? k.states + (size_t)i * 160 : inputs + rec * 160;
 #pragma unroll
             for (int w = 0; w < 5; w++) store_word(dst + w * 32, st[w]);
         }

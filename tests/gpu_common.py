@@ -18,7 +18,8 @@ __all__ = ["KERNELS", "TAG", "TAG4", "CAP", "SITES_PERM", "to_dev", "to_host", "
            "blob_bytes", "EDGE_VALUES", "edge_scalars", "SENTINEL", "Guarded", "guarded_call", "FORM_SIZES", "LEVEL_SIZES",
            "sponge_form", "absorb_form", "level_form", "verify_form", "update_form", "form_family", "oracle_sponge_var",
            "SPONGE_BUCKETS", "COUNT_GRID_RECORDS", "CATALOGUE_LANES", "catalogue_states", "placed_batches", "WIRES",
-           "mont_rows", "perm_many_over", "gadget_check", "assert_wires_are_perm_witness"]
+           "mont_rows", "perm_many_over", "gadget_check", "assert_wires_are_perm_witness", "M64", "GROUP", "_trip_layout",
+           "_bad_messages"]
 
 KERNELS = [1, 2, 3, 4, 5]   # HADES252_KERNEL_LITERAL, _FAST (one state per lane), _COOP (five waves per state), _LANES (one
                             # state per wave, elements spread over 16-lane rows), _ROWS (one state per row, four per wave)
@@ -247,6 +248,41 @@ def oracle_sponge_var(oracle, pool, offsets, lengths, cap, pad, threads=16):
         parts = list(ex.map(lambda a: oracle.sponge_var(pool, offsets[a:a + step], lengths[a:a + step], cap, pad),
                             range(0, n, step)))
     return np.concatenate(parts)
+
+
+# ---------------------------------------------------------------------------------------------
+# ragged sponge batches: trip-count patterns on a form's group boundaries, messages outside the pool (device-free: the GPU
+# tier and the host simulation tier drive the same layouts)
+# ---------------------------------------------------------------------------------------------
+M64 = (1 << 64) - 1
+# messages that share one trip count in each form: the three of a helped block, one per wave (four waves a block)
+# unhelped, the four of a wave in rows, the 64 of a block in coop, the 64 of a wave in the per-lane kernel
+GROUP = {"lanes_helped": 3, "lanes": 4, "rows": 4, "coop": 64, "fast": 64}
+
+
+def _trip_layout(n, group, rng, short=(0, 1, 2, 3, 4, 5, 7, 8, 9, 12, 17)):
+    """Ragged lengths with three patterns aligned to the form's group boundaries, at the start and in the middle of the
+    batch: one long message among short ones, an all-empty group, a group of lengths 0..3 around the pad boundary."""
+    lens = [rng.choice(short) for _ in range(n)]
+    for base in (0, group * (n // group // 2)):
+        if base + 3 * group > n:
+            continue
+        lens[base:base + group] = [1] * group
+        lens[base + group // 2] = 33
+        lens[base + group:base + 2 * group] = [0] * group
+        lens[base + 2 * group:base + 3 * group] = [i % 4 for i in range(group)]
+    return lens
+
+
+def _bad_messages(n, n_pool):
+    """(index, offset, length) of messages that do not lie inside a pool of n_pool scalars, and one that does (an empty
+    message at the very end), for a batch of n >= 16."""
+    return [(n // 7, n_pool - 2, 8),                 # runs past the end
+            (n // 5, n_pool + 1, 4),                 # starts past the end
+            (n // 3, n_pool + 1, 0),                 # starts past the end, empty
+            (n // 2, M64 - 2, 8),                    # offset + length wraps past 2^64
+            (n - 3, 5, M64),                         # length near 2^64 (len + 4 wraps in the sort's bucket)
+            (n - 1, 0, M64 - 3)], (n - 2, n_pool, 0)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -251,10 +251,6 @@ def test_sponge_golden_vectors_on_the_device(torch_cuda, H, oracle, kat):
 # ---------------------------------------------------------------------------------------------
 # every kernel form, guarded outputs, edge values, bad messages, the device sort (tests/gpu_common.py: form table, sizes)
 # ---------------------------------------------------------------------------------------------
-M64 = (1 << 64) - 1
-# messages that share one trip count in each form: the three of a helped block, one per wave (four waves a block)
-# unhelped, the four of a wave in rows, the 64 of a block in coop, the 64 of a wave in the per-lane kernel
-GROUP = {"lanes_helped": 3, "lanes": 4, "rows": 4, "coop": 64, "fast": 64}
 FORM_KERNEL = {"lanes_helped": "k_sponge_lanes<true>", "lanes": "k_sponge_lanes<false>", "rows": "k_sponge_rows",
                "coop": "k_sponge_coop", "fast": "k_sponge"}
 CAPS = [P - 1, 0, R]
@@ -283,31 +279,6 @@ def _sponge_var_dev(torch, hades_lib, dpool, n_scalars, offs, lens, cap, pad, so
     if sort:
         assert bool((scr[sbytes:] == 0xA5).all()), "write past the sort scratch"
     return to_host(got).reshape(n, 4), int(bad.item())
-
-
-def _trip_layout(n, group, rng, short=(0, 1, 2, 3, 4, 5, 7, 8, 9, 12, 17)):
-    """Ragged lengths with three patterns aligned to the form's group boundaries, at the start and in the middle of the
-    batch: one long message among short ones, an all-empty group, a group of lengths 0..3 around the pad boundary."""
-    lens = [rng.choice(short) for _ in range(n)]
-    for base in (0, group * (n // group // 2)):
-        if base + 3 * group > n:
-            continue
-        lens[base:base + group] = [1] * group
-        lens[base + group // 2] = 33
-        lens[base + group:base + 2 * group] = [0] * group
-        lens[base + 2 * group:base + 3 * group] = [i % 4 for i in range(group)]
-    return lens
-
-
-def _bad_messages(n, n_pool):
-    """(index, offset, length) of messages that do not lie inside a pool of n_pool scalars, and one that does (an empty
-    message at the very end), for a batch of n >= 16."""
-    return [(n // 7, n_pool - 2, 8),                 # runs past the end
-            (n // 5, n_pool + 1, 4),                 # starts past the end
-            (n // 3, n_pool + 1, 0),                 # starts past the end, empty
-            (n // 2, M64 - 2, 8),                    # offset + length wraps past 2^64
-            (n - 3, 5, M64),                         # length near 2^64 (len + 4 wraps in the sort's bucket)
-            (n - 1, 0, M64 - 3)], (n - 2, n_pool, 0)
 
 
 @pytest.mark.parametrize("pad", [0, 1])
