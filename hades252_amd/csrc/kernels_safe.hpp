@@ -137,7 +137,8 @@ __global__ void __launch_bounds__(kLanesWaves *kWave) k_safe_lanes(const uint8_t
     }
     const uint8_t *src = in + me * n_in * 32;
     uint8_t *dst = out + me * n_out * 32;
-    uint8_t *mine = states + me * 160 + (lane < 5 ? lane : 0) * 32;
+    // (the one-shot call has no states, and an offset from a null pointer may not even be formed)
+    uint8_t *mine = states != nullptr ? states + me * 160 + (lane < 5 ? lane : 0) * 32 : nullptr;
     const int p = lane - 1;                                            // the position this lane serves (0 .. 3: a word)
     Fr st = lane == 0 ? tag : zero_word();
     if (states != nullptr && lane < 5) st = load_word(mine);

@@ -5,7 +5,8 @@
 // Block emulator: the blocks of a launch run one after another; the threads of a block are real OS threads.
 //   __syncthreads()                    barrier over the block's live threads
 //   __builtin_amdgcn_wave_barrier()    barrier over the live threads of a 64-thread wave
-//   __ballot / __shfl* / readlane / readfirstlane   one exchange slot per wave, between two wave barriers
+//   __ballot / __shfl* / readlane / readfirstlane   an exchange through the wave's slots and one wave barrier
+//   update_dpp (row_shl / row_shr / row_newbcast), permlane16_swap / permlane32_swap   the same: one exchange per move
 //   atomicAdd                          __atomic builtins
 // A thread that returns from the kernel leaves every barrier's participant count and counts as an inactive lane.
 // `__shared__` objects are function-level statics: one per block, because blocks run one at a time.  The dynamic LDS of a
@@ -113,7 +114,9 @@ struct Barrier {
 struct Wave {
     Barrier bar;
     std::atomic<uint64_t> alive{0};      // lanes that have not returned from the kernel
-    uint64_t slot[kWaveSize];            // the exchange slot of ballot / shuffle / readlane
+    uint64_t full = 0;                   // the lanes the wave started with
+    uint64_t slot[2][kWaveSize] = {};    // the exchange slots of ballot / shuffle / readlane / DPP, used alternately
+    uint32_t stamp[2][kWaveSize] = {};   // ... and the number of the exchange each entry was written for
 };
 
 struct Block {
@@ -124,7 +127,8 @@ struct Block {
         for (unsigned w = 0; w < waves.size(); w++) {
             const unsigned n = n_threads - w * kWaveSize < kWaveSize ? n_threads - w * kWaveSize : kWaveSize;
             waves[w].bar.set_live(n);
-            waves[w].alive.store(n == kWaveSize ? ~0ull : (1ull << n) - 1);
+            waves[w].full = n == kWaveSize ? ~0ull : (1ull << n) - 1;
+            waves[w].alive.store(waves[w].full);
         }
     }
 };
@@ -133,6 +137,8 @@ struct Ctx {
     Block *block = nullptr;
     Wave *wave = nullptr;
     int lane = 0;
+    unsigned grid_blocks = 0;
+    unsigned exchanges = 0;              // how many exchanges this lane has taken part in: picks the slot buffer
 };
 inline thread_local Ctx tl_ctx;
 inline uint8_t *g_lds_arena = nullptr;
@@ -142,22 +148,21 @@ inline uint8_t *g_lds_arena = nullptr;
     fflush(stderr);
     abort();
 }
-// The one-state-per-wave and per-row forms (hades_lanes.hpp) move data with DPP / permlane and read s_memtime; they are
-// not emulated.  Their builtins are declared so that the unit compiles, and reaching one ends the run.
+// what the permlane swaps return: element 0 is the new first operand, element 1 the new second
 struct Pair {
     uint32_t v[2];
     uint32_t operator[](int i) const { return v[i]; }
 };
-// With HOSTSIM_SKIP_NOT_EMULATED=1 in the environment the launch is given up instead (its outputs stay as they were), the
-// driver reports it and the run goes on: a whole tree's large levels can then be checked although its small levels run a
-// DPP form.
+// For a builtin that has no emulation (none at present: tests/hostsim/not_emulated.json is empty): it is declared through
+// one of these so that the unit compiles, and reaching it ends the run.  With HOSTSIM_SKIP_NOT_EMULATED=1 in the
+// environment the launch is given up instead (its outputs stay as they were), the driver reports it and the run goes on.
 struct NotEmulated {
     const char *name;
 };
 inline std::atomic<const char *> g_not_emulated{nullptr};
 [[noreturn]] inline void not_emulated(const char *name) {
     static const bool skip = getenv("HOSTSIM_SKIP_NOT_EMULATED") != nullptr;
-    if (!skip) die("form not emulated (needs DPP/permlane/s_memtime)", name);
+    if (!skip) die("form not emulated", name);
     throw NotEmulated{name};
 }
 [[noreturn]] inline int not_emulated_int(const char *name) { not_emulated(name); }
@@ -168,15 +173,33 @@ inline uint8_t *dynamic_lds() { return g_lds_arena; }
 inline void syncthreads() { tl_ctx.block->bar.arrive_and_wait(); }
 inline void wave_barrier() { tl_ctx.wave->bar.arrive_and_wait(); }
 
-// publish my value, wait for the wave, let `read` look at the slots, wait again before anyone overwrites them
+// Publish my value, wait for the wave, let `read` look at the slots.  ONE barrier per exchange: consecutive exchanges use
+// the two slot buffers alternately, so the buffer of exchange i is written again in exchange i + 2 at the earliest, and a
+// lane gets there only through the barrier of exchange i + 1, at which every lane arrives after its reads of exchange i.
+// (Every live lane of a wave takes part in every exchange -- the barrier would not open otherwise -- so the lanes' counts
+// agree.)  A lane is active in an exchange if its entry carries the exchange's number: a lane that has returned from the
+// kernel left an older one, and a lane that returns right after its own reads still counts for the slower readers.
+// A permutation of hades_lanes.hpp is ~13 000 exchanges: a second barrier behind the reads was half of its cost here.
+struct Slots {
+    const uint64_t *value;
+    const uint32_t *stamp;
+    uint32_t number;
+    bool active(int lane) const { return stamp[lane] == number; }
+    uint64_t active_mask() const {
+        uint64_t m = 0;
+        for (int i = 0; i < kWaveSize; i++) m |= (uint64_t)active(i) << i;
+        return m;
+    }
+};
 template <class F>
 inline uint64_t exchange(uint64_t mine, F read) {
     Wave &w = *tl_ctx.wave;
-    w.slot[tl_ctx.lane] = mine;
+    const uint32_t number = ++tl_ctx.exchanges;
+    const int buf = number & 1;
+    w.slot[buf][tl_ctx.lane] = mine;
+    w.stamp[buf][tl_ctx.lane] = number;
     w.bar.arrive_and_wait();
-    const uint64_t r = read(w.slot, w.alive.load());
-    w.bar.arrive_and_wait();
-    return r;
+    return read(Slots{w.slot[buf], w.stamp[buf], number});
 }
 template <class T>
 inline uint64_t to_bits(T v) {
@@ -196,9 +219,7 @@ template <class T>
 inline T shfl(T v, int src, int width) {
     const int lane = tl_ctx.lane;
     const int from = (lane & ~(width - 1)) | (src & (width - 1));
-    return from_bits<T>(exchange(to_bits(v), [from](const uint64_t *s, uint64_t alive) {
-        return (alive >> from) & 1 ? s[from] : 0;
-    }));
+    return from_bits<T>(exchange(to_bits(v), [from](const Slots &s) { return s.active(from) ? s.value[from] : 0; }));
 }
 template <class T>
 inline T shfl_down(T v, unsigned delta, int width) {
@@ -206,21 +227,83 @@ inline T shfl_down(T v, unsigned delta, int width) {
     const int from = lane + (int)delta;
     const bool own = (from & ~(width - 1)) != (lane & ~(width - 1));      // past the group's end: keeps its own value
     const uint64_t mine = to_bits(v);
-    return from_bits<T>(exchange(mine, [=](const uint64_t *s, uint64_t alive) {
-        return own ? mine : ((alive >> from) & 1 ? s[from] : 0);
-    }));
+    return from_bits<T>(exchange(mine, [=](const Slots &s) { return own ? mine : (s.active(from) ? s.value[from] : 0); }));
 }
 inline uint64_t ballot(int pred) {
-    return exchange(pred ? 1 : 0, [](const uint64_t *s, uint64_t alive) {
+    return exchange(pred ? 1 : 0, [](const Slots &s) {
         uint64_t m = 0;
         for (int i = 0; i < kWaveSize; i++)
-            if (((alive >> i) & 1) && s[i]) m |= 1ull << i;
+            if (s.active(i) && s.value[i]) m |= 1ull << i;
         return m;
     });
 }
 template <class T>
 inline T readfirstlane(T v) {
-    return from_bits<T>(exchange(to_bits(v), [](const uint64_t *s, uint64_t alive) { return s[__builtin_ctzll(alive)]; }));
+    return from_bits<T>(exchange(to_bits(v), [](const Slots &s) { return s.value[__builtin_ctzll(s.active_mask())]; }));
+}
+
+// ---- DPP and permlane moves (hades_lanes.hpp): each is ONE wave-wide exchange, the lockstep of a wave as __shfl has it.
+// The hardware's rules for a source lane that is switched off differ per instruction (and per bound_ctrl / fi); no shipped
+// form runs one of these with a lane it could read from gone, so a move that could read a lane that has returned from the
+// kernel ends the run instead of guessing.  `lanes`: what the move of this lane's group can read -- the whole wave for the
+// permlane swaps, the lane's own 16-lane row for the DPP row moves (a row move never leaves its row, so which lanes of
+// OTHER rows are on cannot matter: the unit wrappers of tests/units/arith_units.hip retire whole rows past n).
+// Every one of these moves is a wave barrier of 64 OS threads, and a permutation of hades_lanes.hpp is ~13 000 of them: a
+// block takes seconds.  A whole tree's small levels (up to 4 096 parents: a thousand such blocks) are out of any test's
+// reach, so with HOSTSIM_DPP_MAX_BLOCKS=k in the environment a launch of MORE than k blocks that executes such a move is
+// given up (its outputs stay as they were), the driver reports "over_budget" and the run goes on: the large levels of a
+// tree can then be checked on their own.  Unset: no limit.
+struct OverBudget {};
+inline std::atomic<bool> g_over_budget{false};
+inline void dpp_budget() {
+    static const long limit = [] {
+        const char *e = getenv("HOSTSIM_DPP_MAX_BLOCKS");
+        return e != nullptr ? strtol(e, nullptr, 0) : -1L;
+    }();
+    if (limit >= 0 && (long)tl_ctx.grid_blocks > limit) throw OverBudget{};
+}
+inline void need_lanes(const Slots &s, uint64_t lanes, const char *name) {
+    lanes &= tl_ctx.wave->full;
+    if ((s.active_mask() & lanes) != lanes) die("a lane the move reads had returned from the kernel when the wave executed", name);
+}
+// v_mov_b32_dpp with row_mask = bank_mask = 0xF and bound_ctrl: the row moves of a 16-lane row, zero from outside the row
+inline int update_dpp(int old, int src, int ctrl, int row_mask, int bank_mask, bool bound_ctrl) {
+    static const char *const name = "__builtin_amdgcn_update_dpp";
+    dpp_budget();
+    (void)old;                                                           // with bound_ctrl no lane keeps its old value
+    if (row_mask != 0xF || bank_mask != 0xF || !bound_ctrl) die("masks other than 0xF/0xF, or bound_ctrl off, are not emulated", name);
+    const int lane = tl_ctx.lane, k = lane & 15, row0 = lane & ~15;
+    int from;
+    if (ctrl >= 0x101 && ctrl <= 0x10F) from = k + (ctrl - 0x100);       // row_shl:n   lane k <- lane k + n
+    else if (ctrl >= 0x111 && ctrl <= 0x11F) from = k - (ctrl - 0x110);  // row_shr:n   lane k <- lane k - n
+    else if (ctrl >= 0x150 && ctrl <= 0x15F) from = ctrl - 0x150;        // row_newbcast:n
+    else die("DPP control not emulated (only the row shifts and the row broadcast)", name);
+    const bool in_row = from >= 0 && from < 16;
+    return (int)(uint32_t)exchange((uint32_t)src, [=](const Slots &s) -> uint64_t {
+        need_lanes(s, 0xFFFFull << row0, name);
+        return in_row ? s.value[row0 + from] : 0;
+    });
+}
+// v_permlane16_swap d, s: rows 1, 3 of d <-> rows 0, 2 of s (HALF = 16); v_permlane32_swap: rows 2, 3 of d <-> rows 0, 1
+// of s (HALF = 32).  Both operands travel in one slot (d low, s high); the result is {new d, new s}.
+template <int HALF>
+inline Pair permlane_swap(uint32_t d, uint32_t s, bool fi, bool bound_ctrl, const char *name) {
+    if (fi || bound_ctrl) die("fi / bound_ctrl are not emulated", name);
+    dpp_budget();
+    const int lane = tl_ctx.lane;
+    const bool upper = (lane & HALF) != 0;                               // an upper half of d's, a lower half of s's
+    const uint64_t r = exchange((uint64_t)d | (uint64_t)s << 32, [=](const Slots &sl) -> uint64_t {
+        need_lanes(sl, ~0ull, name);
+        const uint64_t mine = sl.value[lane], peer = sl.value[lane ^ HALF];
+        // upper half: d <- the peer's s, s stays;  lower half: s <- the peer's d, d stays
+        return upper ? (peer >> 32) | (mine & 0xFFFFFFFF00000000ull) : (mine & 0xFFFFFFFFull) | (peer << 32);
+    });
+    return Pair{{(uint32_t)r, (uint32_t)(r >> 32)}};
+}
+// s_memtime: only reached with stamps != nullptr (diagnostic builds); a process-wide counter
+inline unsigned long long memtime() {
+    static std::atomic<unsigned long long> ticks{0};
+    return ticks.fetch_add(1, std::memory_order_relaxed);
 }
 
 // `run` is the kernel call of one thread (hipLaunchKernelGGL below binds the arguments)
@@ -253,10 +336,14 @@ inline void launch(dim3 grid, dim3 block, size_t lds_bytes, F run) {
                 tl_ctx.block = &blk;
                 tl_ctx.wave = &blk.waves[t / kWaveSize];
                 tl_ctx.lane = (int)(t % kWaveSize);
+                tl_ctx.grid_blocks = grid.x;
+                tl_ctx.exchanges = 0;
                 try {
                     run();
                 } catch (const NotEmulated &e) {
                     g_not_emulated.store(e.name);
+                } catch (const OverBudget &) {
+                    g_over_budget.store(true);
                 }
                 // returned (early or at the end): no barrier waits for this lane any more, no exchange sees it
                 tl_ctx.wave->alive.fetch_and(~(1ull << tl_ctx.lane));
@@ -264,7 +351,7 @@ inline void launch(dim3 grid, dim3 block, size_t lds_bytes, F run) {
                 blk.bar.leave();
             });
         for (auto &th : threads) th.join();
-        if (g_not_emulated.load() != nullptr) break;                     // a launch that met a DPP form is given up
+        if (g_not_emulated.load() != nullptr || g_over_budget.load()) break;    // the launch is given up
     }
     ASAN_UNPOISON_MEMORY_REGION(g_lds_arena, kLdsArena);
 }
@@ -280,10 +367,11 @@ inline void launch(dim3 grid, dim3 block, size_t lds_bytes, F run) {
 #define __builtin_amdgcn_readfirstlane(v) hostsim::readfirstlane(v)
 #define __builtin_amdgcn_readlane(v, lane) hostsim::shfl((v), (lane), hostsim::kWaveSize)
 #define __builtin_amdgcn_alignbit(hi, lo, sh) ((uint32_t)((((uint64_t)(hi) << 32) | (uint32_t)(lo)) >> ((sh) & 31)))
-#define __builtin_amdgcn_update_dpp(...) hostsim::not_emulated_int("__builtin_amdgcn_update_dpp")
-#define __builtin_amdgcn_permlane16_swap(...) hostsim::not_emulated_pair("__builtin_amdgcn_permlane16_swap")
-#define __builtin_amdgcn_permlane32_swap(...) hostsim::not_emulated_pair("__builtin_amdgcn_permlane32_swap")
-#define __builtin_amdgcn_s_memtime() hostsim::not_emulated_u64("__builtin_amdgcn_s_memtime")
+#define __builtin_amdgcn_update_dpp(old, src, ctrl, row_mask, bank_mask, bound_ctrl) \
+    hostsim::update_dpp((old), (src), (ctrl), (row_mask), (bank_mask), (bound_ctrl))
+#define __builtin_amdgcn_permlane16_swap(d, s, fi, bc) hostsim::permlane_swap<16>((d), (s), (fi), (bc), "__builtin_amdgcn_permlane16_swap")
+#define __builtin_amdgcn_permlane32_swap(d, s, fi, bc) hostsim::permlane_swap<32>((d), (s), (fi), (bc), "__builtin_amdgcn_permlane32_swap")
+#define __builtin_amdgcn_s_memtime() hostsim::memtime()
 
 template <class T>
 static inline T __shfl(T v, int src, int width = hostsim::kWaveSize) { return hostsim::shfl(v, src, width); }

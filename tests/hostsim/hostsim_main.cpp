@@ -5,7 +5,8 @@
 // host_callers / host_safe / host_cipher); host_fault.hpp stays because the abi_*.hpp files use its HIP_TRY and fault hook.
 // <hip/hip_runtime.h> resolves to the stand-in in this directory (block emulator: see there).  The unit kernels of
 // tests/units/arith_units.hip come along unchanged.  Nothing in this file does arithmetic or defines a kernel: it is a
-// table of entry points and a script reader.
+// table of entry points, a handful of launchers that reach a shipped kernel form at a size the dispatch would not give it
+// (namespace forms), and a script reader.
 //
 // Script (stdin), one command per line:
 //   buf NAME file PATH        NAME = the bytes of PATH, in a heap block of EXACTLY that size (ASan sees byte n)
@@ -13,7 +14,10 @@
 //   buf NAME fill BYTES V     ... or BYTES bytes of value V
 //   call FUNC ARG...          one argument per parameter: a pointer is NAME, NAME+OFFSET or null; an integer is parsed
 //                             prints "rc FUNC VALUE"
-//                             and, with HOSTSIM_SKIP_NOT_EMULATED=1, "not_emulated FUNC BUILTIN" when a launch met a DPP form
+//                             and, with HOSTSIM_SKIP_NOT_EMULATED=1, "not_emulated FUNC BUILTIN" when a launch met a
+//                             builtin the stand-in header has no emulation for (none at present)
+//                             and, with HOSTSIM_DPP_MAX_BLOCKS=k, "over_budget FUNC" when a launch of more than k blocks
+//                             met a DPP / permlane move and was given up (hip/hip_runtime.h says why)
 //   dump NAME PATH            the bytes of NAME -> PATH
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -63,6 +67,136 @@ using namespace hades;
 #include "hades252_amd/csrc/abi_util.hpp"
 
 #include "tests/units/arith_units.hip"
+
+// ---- form launchers -----------------------------------------------------------------------------------------------------
+// The size dispatch gives the unhelped one-per-wave form to 769 .. 1 024 states and the per-row form to 1 025 .. 4 096: at
+// seconds per emulated block no test can afford those sizes.  Each launcher below launches ONE shipped kernel form with the
+// geometry and the arguments of its call site in abi_*.hpp / launch.hpp (copied, and small enough to read side by side), at
+// whatever n the script gives.  form: 0 = one per wave with a helper wave, 1 = one per wave without, 2 = one per row.
+namespace forms {
+enum { kHelped = 0, kUnhelped = 1, kRows = 2 };
+static dim3 lanes_grid(size_t n, int form) {
+    const unsigned per = form == kHelped ? kLanesWaves - 1 : kLanesWaves;
+    return dim3((unsigned)((n + per - 1) / per));
+}
+static dim3 rows_grid(size_t n) { return dim3((unsigned)((n + kRowsWaves * kRowsPerWave - 1) / (kRowsWaves * kRowsPerWave))); }
+static const dim3 kLanesBlock(kLanesWaves *kWave), kRowsBlock(kRowsWaves *kWave);
+#define FORM_LAUNCH(form, helped_k, unhelped_k, rows_k, n, ...)                                                  \
+    do {                                                                                                         \
+        if ((form) == kHelped)                                                                                   \
+            hipLaunchKernelGGL(helped_k, lanes_grid((n), kHelped), kLanesBlock, 0, (hipStream_t) nullptr, __VA_ARGS__);   \
+        else if ((form) == kUnhelped)                                                                            \
+            hipLaunchKernelGGL(unhelped_k, lanes_grid((n), kUnhelped), kLanesBlock, 0, (hipStream_t) nullptr, __VA_ARGS__); \
+        else if ((form) == kRows)                                                                                \
+            hipLaunchKernelGGL(rows_k, rows_grid(n), kRowsBlock, 0, (hipStream_t) nullptr, __VA_ARGS__);         \
+        else                                                                                                     \
+            return HADES252_ERR_INVALID_ARG;                                                                     \
+    } while (0)
+
+#if HOSTSIM_PART & 1
+// abi_perm.hpp: hades252_perm_batch_dev_ex
+static int form_perm(uint8_t *states, size_t n, int form) {
+    FORM_LAUNCH(form, k_perm_lanes<true>, k_perm_lanes<false>, k_perm_rows, n, states, n);
+    return HADES252_OK;
+}
+#endif
+#if HOSTSIM_PART & 2
+// launch.hpp: launch_merkle_lanes / launch_merkle_rows
+static int form_merkle_level(int arity, const uint8_t *children, size_t n_children, uint8_t *parents, size_t n,
+                             const uint64_t *tag_mont, int out_idx, const uint8_t *pad, int form) {
+    const Fr tag = fr_from_u64(tag_mont);
+#define FORM_LEVEL(A)                                                                                            \
+    FORM_LAUNCH(form, (k_merkle_lanes<A, true>), (k_merkle_lanes<A, false>), k_merkle_rows<A>, n, children, n_children, \
+                parents, n, tag, out_idx, pad)
+    switch (arity) {
+        case 1: FORM_LEVEL(1); break;
+        case 2: FORM_LEVEL(2); break;
+        case 3: FORM_LEVEL(3); break;
+        case 4: FORM_LEVEL(4); break;
+        default: return HADES252_ERR_INVALID_ARG;
+    }
+#undef FORM_LEVEL
+    return HADES252_OK;
+}
+// launch.hpp: launch_merkle_update
+static int form_merkle_update(int arity, const uint8_t *children, size_t n_children, uint8_t *parents, const uint64_t *indices,
+                              size_t n_updates, size_t n_leaves, uint64_t span, const uint64_t *tag_mont, int out_idx,
+                              const uint8_t *pad, int form) {
+    const Fr tag = fr_from_u64(tag_mont);
+#define FORM_UPDATE(A)                                                                                           \
+    FORM_LAUNCH(form, (k_merkle_update_lanes<A, true>), (k_merkle_update_lanes<A, false>), k_merkle_update_rows<A>, \
+                n_updates, children, n_children, parents, indices, n_updates, n_leaves, span, tag, out_idx, pad)
+    switch (arity) {
+        case 2: FORM_UPDATE(2); break;
+        case 3: FORM_UPDATE(3); break;
+        case 4: FORM_UPDATE(4); break;
+        default: return HADES252_ERR_INVALID_ARG;
+    }
+#undef FORM_UPDATE
+    return HADES252_OK;
+}
+// abi_merkle.hpp: hades252_merkle_verify_dev
+static int form_merkle_verify(const uint8_t *leaves, const uint64_t *indices, const uint8_t *paths, size_t n_queries,
+                              int depth, int arity, const uint64_t *tag_mont, int out_idx, uint8_t *roots, int form) {
+    const Fr tag = fr_from_u64(tag_mont);
+#define FORM_VERIFY(A)                                                                                           \
+    FORM_LAUNCH(form, (k_merkle_verify_lanes<A, true>), (k_merkle_verify_lanes<A, false>), k_merkle_verify_rows<A>, \
+                n_queries, leaves, indices, paths, n_queries, depth, tag, out_idx, roots)
+    switch (arity) {
+        case 1: FORM_VERIFY(1); break;
+        case 2: FORM_VERIFY(2); break;
+        case 3: FORM_VERIFY(3); break;
+        case 4: FORM_VERIFY(4); break;
+        default: return HADES252_ERR_INVALID_ARG;
+    }
+#undef FORM_VERIFY
+    return HADES252_OK;
+}
+#endif
+#if HOSTSIM_PART & 4
+// abi_sponge.hpp: sponge_launch
+static int form_sponge(const uint8_t *scalars, const uint64_t *offsets, const uint64_t *lengths, size_t n_msgs,
+                       size_t fixed_len, const uint64_t *capacity_mont, int pad_mode, uint8_t *digests, size_t n_scalars,
+                       int *bad_count, int form) {
+    FORM_LAUNCH(form, k_sponge_lanes<true>, k_sponge_lanes<false>, k_sponge_rows, n_msgs, scalars, offsets, lengths, digests,
+                n_msgs, fixed_len, fr_from_u64(capacity_mont), pad_mode, n_scalars, bad_count);
+    return HADES252_OK;
+}
+// abi_sponge.hpp: hades252_sponge_absorb_dev
+static int form_sponge_absorb(uint8_t *states, const uint8_t *blocks, size_t n, int blocks_each, int form) {
+    FORM_LAUNCH(form, k_sponge_absorb_lanes<true>, k_sponge_absorb_lanes<false>, k_sponge_absorb_rows, n, states, blocks, n,
+                blocks_each);
+    return HADES252_OK;
+}
+// abi_cipher.hpp: cipher_launch (there is no per-row cipher)
+static int form_cipher(int decrypt, const uint8_t *in, const uint8_t *keys, const uint8_t *nonces, size_t n, size_t len,
+                       const uint64_t *domain_mont, uint8_t *out, uint8_t *ok, int *rejected, int form) {
+    const Fr dom = fr_from_u64(domain_mont), lw = fr_mont_of_u64(len);
+    if (form == kRows) return HADES252_ERR_INVALID_ARG;
+    if (decrypt)
+        FORM_LAUNCH(form, (k_cipher_lanes<true, true>), (k_cipher_lanes<true, false>), (k_cipher_lanes<true, false>), n, in,
+                    keys, nonces, out, ok, rejected, n, len, dom, lw);
+    else
+        FORM_LAUNCH(form, (k_cipher_lanes<false, true>), (k_cipher_lanes<false, false>), (k_cipher_lanes<false, false>), n, in,
+                    keys, nonces, out, ok, rejected, n, len, dom, lw);
+    return HADES252_OK;
+}
+// abi_safe.hpp: safe_launch behind hades252_safe_hash_dev (states == NULL) and safe_stream (one call from *cursor on)
+static int form_safe(const uint8_t *in, uint8_t *out, uint8_t *states, size_t n, const uint32_t *calls, size_t n_calls,
+                     uint32_t *cursor, const uint64_t *tag_mont, int form) {
+    SafePlan plan;
+    const uint32_t start = cursor != nullptr ? *cursor : 0;
+    if (form == kRows || !safe_plan(calls, n_calls, start, plan)) return HADES252_ERR_INVALID_ARG;
+    const Fr tag = tag_mont != nullptr ? fr_from_u64(tag_mont) : Fr{};
+    FORM_LAUNCH(form, k_safe_lanes<true>, k_safe_lanes<false>, k_safe_lanes<false>, n, in, out, states, n, plan.n_in, plan.n_out,
+                plan.calls, plan.n_calls, start, plan.n_perms, tag);
+    if (cursor != nullptr) *cursor = plan.cursor_out;
+    return HADES252_OK;
+}
+#endif
+#undef FORM_LAUNCH
+}  // namespace forms
+using namespace forms;
 #pragma clang attribute pop
 
 #include <functional>
@@ -121,6 +255,7 @@ static void reg(const char *name, R (*fn)(A...)) {
         (void)i;
         const R r = std::apply(fn, args);
         if (const char *what = hostsim::g_not_emulated.exchange(nullptr)) printf("not_emulated %s %s\n", name, what);
+        if (hostsim::g_over_budget.exchange(false)) printf("over_budget %s\n", name);
         if constexpr (std::is_pointer_v<R>)
             printf("rc %s %s\n", name, r ? (const char *)r : "(null)");
         else
@@ -148,6 +283,8 @@ static void register_all() {
     REG(hades252_quintic_s_box_dev); REG(hades252_from_bytes_dev); REG(hades252_to_bytes_dev);
     // launch.hpp: the launcher the host-pointer path uses with out != in (no device-pointer entry point reaches that shape)
     REG(launch_perm_fast);
+    // ... and the forms whose dispatch sizes cost minutes here (above)
+    REG(form_perm);
 #endif
 #if HOSTSIM_PART & 2
     // abi_merkle.hpp
@@ -158,6 +295,7 @@ static void register_all() {
     REG(hades252_merkle_update_dev); REG(hades252_merkle_empty_digests_dev); REG(hades252_merkle_open_pad_dev);
     REG(hades252_merkle_open_dev); REG(hades252_merkle_verify_dev); REG(hades252_merkle_forest_scratch_bytes);
     REG(hades252_merkle_forest_dev);
+    REG(form_merkle_level); REG(form_merkle_update); REG(form_merkle_verify);
 #endif
 #if HOSTSIM_PART & 4
     // abi_sponge.hpp
@@ -168,6 +306,7 @@ static void register_all() {
     REG(hades252_cipher_encrypt_dev); REG(hades252_cipher_decrypt_dev);
     // abi_safe.hpp
     REG(hades252_safe_pattern); REG(hades252_safe_hash_dev); REG(hades252_safe_absorb_dev); REG(hades252_safe_squeeze_dev);
+    REG(form_sponge); REG(form_sponge_absorb); REG(form_cipher); REG(form_safe);
 #endif
 #if HOSTSIM_PART & 8
     // abi_witness.hpp
@@ -182,11 +321,13 @@ static void register_all() {
     REG(hades252_gen_b_dev); REG(hades252_gen_a_dev); REG(hades252_digest_dev);
 #endif
 #if HOSTSIM_PART & 1
-    // tests/units/arith_units.hip (the per-lane routines; the units_lane_* ones need DPP and are not emulated)
+    // tests/units/arith_units.hip
     REG(units_to_f29); REG(units_from_f29); REG(units_mont_mul); REG(units_mont_sqr); REG(units_mont_mul_const);
     REG(units_mont_mul_small); REG(units_mont_lin); REG(units_mont_lin1); REG(units_sbox29); REG(units_add_lazy);
     REG(units_small_mds); REG(units_finalize); REG(units_finalize1); REG(units_finalize32); REG(units_mds_row_cols);
     REG(units_fr_add); REG(units_fr_cond_sub_p); REG(units_fr_mul); REG(units_fr_is_canonical);
+    REG(units_lane_mont_mul); REG(units_lane_sbox); REG(units_lane_lin); REG(units_lane_mds_row); REG(units_carry_split);
+    REG(units_dpp_moves);
 #endif
 }
 

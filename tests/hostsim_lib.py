@@ -49,6 +49,15 @@ REWRITES = {
     # have stored before the next read.  No effect on a machine that runs the wave in lockstep.
     "wave_lockstep_store": (re.compile(r"^(\s*)parked_slot\[wave \+ z\] = slot;", re.M),
                             r"\1hostsim::wave_barrier(); parked_slot[wave + z] = slot; hostsim::wave_barrier();"),
+    # lanes_perm / rows_perm end with every lane reading a word of the wave's io area (lanes without a word of their own read
+    # word 0) and begin with lanes 0..4 / 0..19 storing their input word there.  In a chain kernel (sponge, cipher, duplex
+    # sponge: one permutation after another in one wave) nothing but program order lies between that read and the next
+    # permutation's store: on gfx950 a wave issues the read for all 64 lanes before the later store instruction and the LDS
+    # unit serves a wave's requests in order.  OS threads have no such lockstep, so the emulator gets the wave-level order as
+    # a barrier in front of the store (found by TSan on k_sponge_lanes<true>).  No effect on a machine that runs the wave in
+    # lockstep.
+    "wave_lockstep_input": (re.compile(r"^    if \(lane < (5|20)\) \{$", re.M),
+                            r"    hostsim::wave_barrier(); if (lane < \1) {"),
 }
 
 FLAGS = {
@@ -60,7 +69,8 @@ FLAGS = {
 PARTS = {"perm": 1, "merkle": 2, "sponge": 4, "witness": 8}
 COMMON = ["-x", "c++", "-std=c++17", "-pthread", "-Wno-unused-function", "-Wno-unused-value"]
 
-# name -> (file relative to the root, exact text, replacement): each must match exactly once in the rewritten copy
+# name -> (file relative to the root, exact text, replacement), or a list of such edits that belong together: each must
+# match exactly once in the rewritten copy
 MUTANTS = {
     # ASan: the ragged tail of a store runs one 16-byte chunk past an exact-size buffer
     "store_off_by_one": (os.path.join("hades252_amd", "csrc", "staging.hpp"),
@@ -85,7 +95,34 @@ MUTANTS = {
     "double_doubled": (os.path.join("hades252_amd", "csrc", "hades_fast.hpp"),
                        "                if (i < j) mac(acc, a.l[i], d[j]);",
                        "                if (i < j) { mac(acc, a.l[i], d[j]); mac(acc, a.l[i], d[j]); }"),
+    # TSan: both sides of the helper protocol of the helped one-state-per-wave form use ONE exchange buffer instead of the
+    # ping-pong pair, so a main wave publishes round r + 1 while the helper may still be reading round r (hades_lanes.hpp,
+    # the comment of LanesLds::xw)
+    "xw_single_buffer": [(os.path.join("hades252_amd", "csrc", "hades_lanes.hpp"),
+                          "        uint32_t (&xw)[16][8] = L.xw[HELPED ? par : 0];",
+                          "        uint32_t (&xw)[16][8] = L.xw[HELPED ? par * 0 : 0];"),
+                         (os.path.join("hades252_amd", "csrc", "hades_lanes.hpp"),
+                          "        uint32_t (&xw)[16][8] = L.xw[i < 4 ? (i & 1) : ((i + 1) & 1)];",
+                          "        uint32_t (&xw)[16][8] = L.xw[0 * i];")],
+    # oracle mismatch: the light carry pass of the lane form's linear layer takes the carry one bit too high; every value
+    # stays inside its machine word, so no sanitizer has anything to see
+    "carry_light_shift": (os.path.join("hades252_amd", "csrc", "hades_lanes.hpp"),
+                          "    const uint32_t h = t >> kLB;\n    c16 = h;",
+                          "    const uint32_t h = t >> (kLB + 1);\n    c16 = h;"),
+    # ASan: lane w of a state wave addresses word w + 1 of its state, so word 4 of the LAST state lies behind the buffer
+    "lanes_word_off_by_one": (os.path.join("hades252_amd", "csrc", "kernels_perm.hpp"),
+                              "    uint8_t *mine = states + rec * 160 + (lane < 5 ? lane : 0) * 32;\n"
+                              "    const Fr in = lane < 5 ? load_word(mine) : zero_word();\n"
+                              "    const Fr out = lanes_perm<HELPED>",
+                              "    uint8_t *mine = states + rec * 160 + (lane < 5 ? lane + 1 : 0) * 32;\n"
+                              "    const Fr in = lane < 5 ? load_word(mine) : zero_word();\n"
+                              "    const Fr out = lanes_perm<HELPED>"),
 }
+
+
+def mutant_edits(name) -> list:
+    m = MUTANTS[name]
+    return list(m) if isinstance(m, list) else [m]
 
 
 def _strip_comments(text: str) -> str:
@@ -104,8 +141,9 @@ def rewritten(rel: str, mutant=None) -> str:
         text = f.read()
     for pattern, repl in REWRITES.values():
         text = pattern.sub(repl, text)
-    if mutant is not None and MUTANTS[mutant][0] == rel:
-        _, old, new = MUTANTS[mutant]
+    for where, old, new in (mutant_edits(mutant) if mutant is not None else []):
+        if where != rel:
+            continue
         if text.count(old) != 1:
             raise RuntimeError("mutant %s: its text occurs %d times in %s, not once" % (mutant, text.count(old), rel))
         text = text.replace(old, new)
@@ -181,7 +219,8 @@ def build(variant: str = "asan", part: str = "perm", mutant=None, verbose: bool 
 # every executable the tests use: (variant, part, mutant).  TSan runs the perm, merkle and sponge parts; the mutants live
 # in the perm part (k_perm_fast through the shipped launcher, and the unit wrappers).
 MUTANT_VARIANT = {"store_off_by_one": "asan", "lds_halved": "asan", "load_barrier_removed": "tsan", "negp_index": "asan",
-                  "double_doubled": "asan"}
+                  "double_doubled": "asan", "xw_single_buffer": "tsan", "carry_light_shift": "asan",
+                  "lanes_word_off_by_one": "asan"}
 ALL_BUILDS = [("asan", p, None) for p in PARTS] + [("tsan", p, None) for p in ("perm", "merkle", "sponge")] + \
              [(v, "perm", m) for m, v in MUTANT_VARIANT.items()]
 BUILD_JOBS = 6          # compilers side by side in build_all (a fixed number, not the machine's CPU count)

@@ -723,6 +723,39 @@ def row_bcast(v, n):
     return [v[n]] * 16
 
 
+def wave_bcast_row(v, row):
+    """wave_bcast_row<ROW> of hades_lanes.hpp on the 64 lanes of a wave: every row <- row ROW."""
+    return list(v[16 * row:16 * row + 16]) * 4
+
+
+def permlane_swap(d, s, half):
+    """v_permlane16_swap d, s (half = 16: rows 1, 3 of d <-> rows 0, 2 of s) and v_permlane32_swap d, s (half = 32: rows
+    2, 3 of d <-> rows 0, 1 of s) on two 64-lane registers -> (new d, new s)."""
+    nd, ns = list(d), list(s)
+    for lane in range(64):
+        if lane & half:
+            nd[lane], ns[lane - half] = s[lane - half], d[lane]
+    return nd, ns
+
+
+def test_wave_bcast_row_is_two_half_exchanges():
+    """The statements of wave_bcast_row<ROW> (permlane16_swap(v, v) -> half ROW -> permlane32_swap(h, h) -> first half)
+    give every row the wave's row ROW; and a swap done twice is the identity."""
+    v, s = list(range(100, 164)), list(range(500, 564))
+    for row in (0, 1):
+        h = permlane_swap(v, v, 16)[row]
+        assert permlane_swap(h, h, 32)[0] == wave_bcast_row(v, row) == [100 + 16 * row + k for k in range(16)] * 4
+    for half in (16, 32):
+        nd, ns = permlane_swap(v, s, half)
+        assert sorted(nd + ns) == sorted(v + s) and (nd, ns) != (v, s)
+        assert permlane_swap(nd, ns, half) == (v, s)
+    nd, ns = permlane_swap(v, s, 16)
+    assert nd[16:32] == s[0:16] and nd[48:64] == s[32:48] and ns[0:16] == v[16:32] and ns[32:48] == v[48:64]
+    assert nd[0:16] == v[0:16] and nd[32:48] == v[32:48] and ns[16:32] == s[16:32] and ns[48:64] == s[48:64]
+    nd, ns = permlane_swap(v, s, 32)
+    assert nd[32:64] == s[0:32] and ns[0:32] == v[32:64] and nd[0:32] == v[0:32] and ns[32:64] == s[32:64]
+
+
 def u64(x):
     assert 0 <= x < U64, "unsigned 64-bit column overflow"
     return x

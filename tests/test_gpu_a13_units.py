@@ -631,3 +631,30 @@ def test_carry_split_vs_model(torch_cuda, units):
         assert sum(x << (LB * i) for i, x in enumerate(t[k])) + (mu[15] << (LB * 16)) + (mtp[15] << (LB * 17)) == \
             sum(x << (LB * i) for i, x in enumerate(acc))                   # the carry step keeps the row's value
     driven("carry_split", n)
+
+
+def test_dpp_moves_vs_model(torch_cuda, units):
+    """The data moves every lane routine is made of, on their own: row_shr / row_shl<1..15>, row_bcast<0..15>,
+    wave_bcast_row<0 / 1> and the two raw half-exchanges with two different operands, on lane-distinct non-zero values
+    (a zero can then only be a shift's fill), two waves.  tests/test_hostsim_units.py holds the host build's emulation of
+    these builtins to the same model."""
+    torch = torch_cuda
+    n = 2
+    a = [0x1000_0000 * (w + 1) + 0x0101 * (lane + 1) for w in range(n) for lane in range(64)]
+    b = [0xB000_0000 + 0x0100_0000 * w + 0x0307 * (lane + 1) for w in range(n) for lane in range(64)]
+    assert len(set(a + b)) == 2 * 64 * n and 0 not in a + b
+    o = Out(torch, n, 64 * 52)
+    call(torch, units.units_dpp_moves, put(torch, a, np.uint32), put(torch, b, np.uint32), o, n)
+    got = (o.get().astype(np.int64) & 0xFFFFFFFF).reshape(n, 52, 64)
+    for w in range(n):
+        va, vb = a[64 * w:64 * w + 64], b[64 * w:64 * w + 64]
+        rows = [va[16 * r:16 * r + 16] for r in range(4)]
+        exp = [sum((M.row_shr(r, s) for r in rows), []) for s in range(1, 16)]
+        exp += [sum((M.row_shl(r, s) for r in rows), []) for s in range(1, 16)]
+        exp += [sum((M.row_bcast(r, s) for r in rows), []) for s in range(16)]
+        exp += [M.wave_bcast_row(va, 0), M.wave_bcast_row(va, 1)]
+        exp += list(M.permlane_swap(va, vb, 16)) + list(M.permlane_swap(va, vb, 32))
+        assert len(exp) == 52
+        for j, e in enumerate(exp):
+            assert list(map(int, got[w, j])) == e, (w, j)
+    driven("row_shr / row_shl / row_bcast / wave_bcast_row / permlane swaps", 52 * n)

@@ -404,3 +404,209 @@ def test_merkle_open_witness(oracle):
     assert (u64(r.out["mo_inputs"]).reshape(exp.shape) == exp).all()
     assert int(np.frombuffer(r.out["bad"], dtype=np.int32)[0]) == 1
     assert_wires(r, "mo_inputs", "mo_wires")
+
+
+# ---- the DPP forms of hades_lanes.hpp: one chain per wave (with a helper wave, and without) and per 16-lane row ----------
+# A permutation of one emulated block costs seconds (tests/hostsim/hip/hip_runtime.h), a chain several of them: the sizes
+# are the smallest that reach every role of a block -- 1 (a lone state wave and its helper), 3 (a full helped block), 4 (a
+# second block with idle waves), 5 for the unhelped form (a second block whose other waves return at once), 4 and 5 for the
+# rows form (a full wave, a second wave with one row in use) -- and the longest chain sits where it is cheapest.  The
+# helped form is what the dispatch gives these sizes; the unhelped form (769 .. 1 024) and the rows form (1 025 .. 4 096)
+# are launched with their call sites' geometry by the form_* launchers (tests/hostsim/hostsim_main.cpp, namespace forms).
+HELPED, UNHELPED, PER_ROW = 0, 1, 2
+assert 5 < FORM_SIZES["lanes"][0] < FORM_SIZES["rows"][0] and FORM_SIZES["lanes_helped"][0] == 1
+
+
+def clean(r):
+    return "over_budget" not in r.stdout and "not_emulated" not in r.stdout
+
+
+@pytest.mark.parametrize("form,lens,pad", [(HELPED, [3], 0), (HELPED, [5, 5, 5], 1), (HELPED, [9, 2, 5, 3], 1),
+                                           (UNHELPED, [5, 0, 2, 1, 4], 1), (PER_ROW, [9, 0, 5, 3], 1), (PER_ROW, [3] * 5, 0)],
+                         ids=["helped-1", "helped-3", "helped-4-three_blocks-out_of_pool", "unhelped-5", "rows-4-three_blocks",
+                              "rows-5"])
+def test_sponge_one_message_per_wave_and_per_row(oracle, form, lens, pad):
+    """k_sponge_lanes<true> / <false> and k_sponge_rows: equal lengths go in as a fixed-length batch, unequal ones as a
+    ragged one over a pool (a message of three blocks beside shorter ones: every wave of a helped block runs the block's
+    maximum and latches its digest after its own last block); in the helped ragged case message 1 lies outside the pool,
+    is counted and hashed as the empty message."""
+    n = len(lens)
+    assert sponge_form(n) == ("k_sponge_lanes<true>",) or form != HELPED
+    fixed = len(set(lens)) == 1
+    n_pool = sum(lens) + 3
+    pool = edge_scalars(n_pool, 700 + n + pad)
+    offs = np.cumsum([0] + lens[:-1]).astype(np.uint64)
+    la = np.array(lens, dtype=np.uint64)
+    bad = 0
+    if form == HELPED and not fixed:
+        offs[1], bad = n_pool - 1, 1                      # two words from the last word of the pool
+    so, sl = offs.copy(), la.copy()
+    if bad:
+        so[1], sl[1] = 0, 0
+    s = HS.Script("sponge")
+    s.buf("cap", limbs(CAP))
+    s.fill("dig", 32 * n, 0xFF)
+    s.zero("bad", 4)
+    if fixed:
+        msgs = pool[:4 * n * lens[0]]
+        s.buf("msgs", msgs.tobytes())
+        exp = oracle.sponge(msgs, lens[0], CAP, pad)
+        if form == HELPED:
+            s.call("hades252_sponge_hash_dev", "msgs", n, lens[0], "cap", pad, "dig", None)
+        else:
+            s.call("form_sponge", "msgs", None, None, n, lens[0], "cap", pad, "dig", n * lens[0], None, form)
+    else:
+        s.buf("pool", pool.tobytes())
+        s.buf("offs", offs.tobytes())
+        s.buf("lens", la.tobytes())
+        exp = oracle.sponge_var(pool, so, sl, CAP, pad)
+        if form == HELPED:
+            s.call("hades252_sponge_hash_var_dev", "pool", n_pool, "offs", "lens", n, "cap", pad, "dig", "bad", None)
+        else:
+            s.call("form_sponge", "pool", "offs", "lens", n, 0, "cap", pad, "dig", n_pool, "bad", form)
+    s.dump("dig")
+    s.dump("bad")
+    r = s.run(timeout=900)                               # measured: 2 .. 22 s
+    assert [rc for _, rc in r.rc] == [0] and clean(r)
+    assert int(np.frombuffer(r.out["bad"], dtype=np.int32)[0]) == bad
+    assert (u64(r.out["dig"]) == exp).all()
+
+
+@pytest.mark.parametrize("form,n,blocks", [(HELPED, 1, 3), (HELPED, 3, 2), (HELPED, 4, 1), (UNHELPED, 5, 1), (PER_ROW, 4, 1),
+                                           (PER_ROW, 5, 2)])
+def test_sponge_streaming_one_state_per_wave_and_per_row(oracle, form, n, blocks):
+    """k_sponge_absorb_lanes<true> / <false> and k_sponge_absorb_rows between init and squeeze: the digest of the
+    zero-filled fixed-length sponge over the same words, and the whole state written back."""
+    msg_len = 4 * blocks - 1
+    msgs = edge_scalars(n * msg_len, 710 + n).reshape(n, msg_len, 4)
+    blk = np.zeros((n, 4 * blocks, 4), dtype=np.uint64)
+    blk[:, :msg_len] = msgs
+    s = HS.Script("sponge")
+    s.buf("cap", limbs(CAP))
+    s.fill("st", 160 * n, 0xFF)
+    s.buf("blk", blk.tobytes())
+    s.fill("dig", 32 * n, 0xFF)
+    s.call("hades252_sponge_init_dev", "st", n, "cap", None)
+    if form == HELPED:
+        assert absorb_form(n) == "k_sponge_absorb_lanes<true>"
+        s.call("hades252_sponge_absorb_dev", "st", "blk", n, blocks, None)
+    else:
+        s.call("form_sponge_absorb", "st", "blk", n, blocks, form)
+    s.call("hades252_sponge_squeeze_dev", "st", "dig", n, 1, None)
+    s.dump("dig")
+    s.dump("st")
+    r = s.run(timeout=900)                               # measured: 3 .. 12 s
+    assert [rc for _, rc in r.rc] == [0, 0, 0] and clean(r)
+    assert (u64(r.out["dig"]) == oracle.sponge(msgs.reshape(-1), msg_len, CAP, 0)).all()
+    # the state: absorbing block by block with the oracle's permutation
+    st = np.zeros((n, 5, 4), dtype=np.uint64)
+    st[:, 0] = limbs_of(CAP)
+    for b in range(blocks):
+        for j in range(4):
+            st[:, 1 + j] = CM.fr_add(st[:, 1 + j], blk[:, 4 * b + j])
+        st = oracle.perm_batch(st.reshape(-1)).reshape(n, 5, 4)
+    assert (u64(r.out["st"]).reshape(n, 5, 4) == st).all()
+
+
+@pytest.mark.parametrize("form,n,m", [(HELPED, 1, 5), (HELPED, 3, 1), (HELPED, 4, 2), (UNHELPED, 4, 1)])
+def test_cipher_one_message_per_wave(oracle, form, n, m):
+    """k_cipher_lanes, encrypt and decrypt.  The decrypt launch gets the ciphers with message 0 tampered (its tag when it
+    is the only one, else a word), and from two messages on message 1 non-canonical (word 0 + p or 2^256 - 1), message 2
+    intact, message 3 with a wrong tag: rejected messages come out as zeros and are counted, the intact one round-trips."""
+    msgs, keys, nonces = cipher_inputs(n, m, 720 + n)
+    exp_c = CM.encrypt_batch(msgs, keys, nonces, m, oracle.perm_batch)
+    t = exp_c.copy()
+    t[0, m if n == 1 else 0, 0] ^= np.uint64(1)
+    if n > 1:
+        v = oracle_lib.int_of(t[1, 0]) + P
+        t[1, 0] = CM.limbs(v if v < (1 << 256) else (1 << 256) - 1)
+    if n > 3:
+        t[3, m, 1] ^= np.uint64(1 << 40)
+    exp_m, exp_ok = CM.decrypt_batch(t, keys, nonces, m, oracle.perm_batch)
+    assert list(exp_ok) == [0, 0, 1, 0][:n]
+    s = HS.Script("sponge")
+    for name, a in (("msgs", msgs), ("keys", keys), ("nonces", nonces), ("t", t)):
+        s.buf(name, a.tobytes())
+    s.buf("dom", limbs(CM.DOMAIN_MONT))
+    s.fill("c", 32 * n * (m + 1), 0xFF)
+    s.fill("back", 32 * n * m, 0xFF)
+    s.fill("ok", n, 0xFF)
+    s.zero("rej", 4)
+    if form == HELPED:
+        s.call("hades252_cipher_encrypt_dev", "msgs", "keys", "nonces", n, m, "dom", "c", None)
+        s.call("hades252_cipher_decrypt_dev", "t", "keys", "nonces", n, m, "dom", "back", "ok", "rej", None)
+    else:
+        s.call("form_cipher", 0, "msgs", "keys", "nonces", n, m, "dom", "c", None, None, form)
+        s.call("form_cipher", 1, "t", "keys", "nonces", n, m, "dom", "back", "ok", "rej", form)
+    for b in ("c", "back", "ok", "rej"):
+        s.dump(b)
+    r = s.run(timeout=900)                               # measured: 13 .. 28 s
+    assert [rc for _, rc in r.rc] == [0, 0] and clean(r)
+    assert (u64(r.out["c"]).reshape(exp_c.shape) == exp_c).all()
+    assert (u64(r.out["back"]).reshape(exp_m.shape) == exp_m).all()
+    assert (np.frombuffer(r.out["ok"], dtype=np.uint8) == exp_ok).all()
+    assert int(np.frombuffer(r.out["rej"], dtype=np.int32)[0]) == int((exp_ok == 0).sum())
+
+
+def safe_script(s, form, k, pat, inp, n, one_shot, streaming):
+    """the calls of pattern `pat` on n sponges: the whole pattern in one launch and / or call by call over the states"""
+    n_out = SM.words_out(pat)
+    s.buf("in%d" % k, inp.tobytes())
+    s.buf("calls%d" % k, calls_buf(pat))
+    if one_shot:
+        s.fill("out%d" % k, 32 * n * n_out, 0xFF)
+        if form == HELPED:
+            s.call("hades252_safe_hash_dev", "in%d" % k, n, "calls%d" % k, len(pat), "tag", "out%d" % k, None)
+        else:
+            s.call("form_safe", "in%d" % k, "out%d" % k, None, n, "calls%d" % k, len(pat), None, "tag", form)
+        s.dump("out%d" % k)
+    if streaming:
+        s.fill("st%d" % k, 160 * n, 0xFF)
+        s.zero("cur%d" % k, 4)
+        s.call("hades252_sponge_init_dev", "st%d" % k, n, "tag", None)
+        at = 0
+        for j, (kind, ln) in enumerate(pat):
+            one = np.array(SM.encode([(kind, ln)]), dtype=np.uint32).tobytes()
+            s.buf("call%d_%d" % (k, j), one)
+            if kind == "absorb":
+                s.buf("si%d_%d" % (k, j), np.ascontiguousarray(inp[:, at:at + ln]).tobytes())
+                if form == HELPED:
+                    s.call("hades252_safe_absorb_dev", "st%d" % k, n, "si%d_%d" % (k, j), ln, "cur%d" % k, None)
+                else:
+                    s.call("form_safe", "si%d_%d" % (k, j), None, "st%d" % k, n, "call%d_%d" % (k, j), 1, "cur%d" % k, None, form)
+                at += ln
+            else:
+                s.fill("so%d_%d" % (k, j), 32 * n * ln, 0xFF)
+                if form == HELPED:
+                    s.call("hades252_safe_squeeze_dev", "st%d" % k, n, ln, "so%d_%d" % (k, j), "cur%d" % k, None)
+                else:
+                    s.call("form_safe", None, "so%d_%d" % (k, j), "st%d" % k, n, "call%d_%d" % (k, j), 1, "cur%d" % k, None, form)
+                s.dump("so%d_%d" % (k, j))
+
+
+@pytest.mark.parametrize("form,n,patterns,one_shot,streaming", [
+    (HELPED, 1, [0, 1, 2, 3, 4], True, False), (HELPED, 1, [0, 1, 2, 3, 4], False, True), (HELPED, 3, [1], False, True),
+    (HELPED, 4, [2], True, False), (UNHELPED, 5, [0], True, True)],
+    ids=["helped-1-one_shot", "helped-1-streaming", "helped-3-streaming", "helped-4-one_shot", "unhelped-5-both"])
+def test_duplex_sponge_one_sponge_per_wave(oracle, form, n, patterns, one_shot, streaming):
+    """k_safe_lanes over the patterns of test_duplex_sponge_one_shot_and_streaming: the whole pattern in one launch (no
+    states: from the second sponge of a launch on this is where the kernel used to form states + offset from a null
+    pointer) and call by call over the streaming states."""
+    tag = S.to_mont(0x1234)
+    s = HS.Script("sponge")
+    s.buf("tag", limbs(tag))
+    want = {}
+    for k in patterns:
+        pat = SAFE_PATTERNS[k]
+        inp = edge_scalars(n * SM.words_in(pat), 730 + 10 * n + k).reshape(n, SM.words_in(pat), 4)
+        want[k] = SM.run_batch(pat, inp, tag, oracle.perm_batch)
+        safe_script(s, form, k, pat, inp, n, one_shot, streaming)
+    r = s.run(timeout=1200)                              # measured: 11 .. 28 s
+    assert all(rc == 0 for _, rc in r.rc) and clean(r)
+    for k in patterns:
+        pat = SAFE_PATTERNS[k]
+        if one_shot:
+            assert (u64(r.out["out%d" % k]).reshape(want[k].shape) == want[k]).all(), pat
+        if streaming:
+            pieces = [u64(r.out["so%d_%d" % (k, j)]).reshape(n, ln, 4) for j, (kind, ln) in enumerate(pat) if kind == "squeeze"]
+            assert (np.concatenate(pieces, axis=1) == want[k]).all(), pat

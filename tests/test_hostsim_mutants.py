@@ -4,6 +4,7 @@ the unchanged build, and asserts that the detector named for the mutant reports 
 tree's sources."""
 import json
 import os
+import re
 import sys
 
 import numpy as np
@@ -91,3 +92,51 @@ def test_doubled_cross_products_are_a_ubsan_report():
     assert [list(map(int, r)) for r in got] == [M.mont_fips(x, x, True) for x in M.PRODUCT_PATTERNS]
     assert bad.returncode != 0 and "runtime error: signed integer overflow" in bad.stderr
     assert "hades_fast.hpp" in bad.stderr
+
+
+# ---- the DPP forms of hades_lanes.hpp (emulated DPP row moves and permlane swaps) ---------------------------------------
+LANES = 4
+
+
+def lanes_script(variant, mutant, n, seed=701):
+    s = HS.Script("perm", variant, mutant)
+    s.buf("st", edge_scalars(5 * n, seed).tobytes())
+    s.call("hades252_perm_batch_dev_ex", "st", n, None, LANES)
+    s.dump("st")
+    return s
+
+
+def test_single_exchange_buffer_of_the_helper_protocol_is_a_tsan_report():
+    """The one cross-wave protocol argued in prose only (LanesLds::xw, "whatever the timing"): with both sides on ONE
+    buffer a main wave's store of round r + 1 is no longer a barrier away from the helper's reads of round r.  TSan's
+    happens-before analysis reports it whatever the schedule of this run was."""
+    _, bad = both(lambda m: lanes_script("tsan", m and "xw_single_buffer", 4), 600)    # measured: 9 s, the mutant 0.6 s
+    assert bad.returncode != 0 and "ThreadSanitizer: data race" in bad.stderr
+    assert "lanes_perm" in bad.stderr and "hades_lanes.hpp" in bad.stderr
+
+
+def test_wrong_carry_shift_in_a_dpp_routine_is_an_oracle_mismatch():
+    with open(os.path.join(ROOT, "tests", "golden", "kat.json")) as f:
+        kat = json.load(f)["single"]
+    inp = np.array([l for s in kat for x in s["in_mont"] for l in limbs_of(int(x, 16))], dtype=np.uint64)
+    exp = np.array([l for s in kat for x in s["out_mont"] for l in limbs_of(int(x, 16))], dtype=np.uint64)
+
+    def make(m):
+        s = HS.Script("perm", "asan", m and "carry_light_shift")
+        s.buf("st", inp.tobytes())
+        s.call("hades252_perm_batch_dev_ex", "st", len(kat), None, LANES)
+        s.dump("st")
+        return s
+    good, bad = both(make, 900)                              # measured: 25 s each (11 known answers: four helped blocks)
+    assert (np.frombuffer(good.out["st"], dtype=np.uint64) == exp).all()
+    assert bad.returncode == 0, bad.stderr[-2000:]          # every value stays inside its word: only the known answers see it
+    got = np.frombuffer(bad.out["st"], dtype=np.uint64).reshape(-1, 20)
+    assert (got != exp.reshape(-1, 20)).any(axis=1).all()   # every known answer is missed
+
+
+def test_lane_addressing_the_next_word_is_an_asan_report():
+    _, bad = both(lambda m: lanes_script("asan", m and "lanes_word_off_by_one", 1), 300)      # measured: 2 s
+    assert bad.returncode != 0 and "AddressSanitizer: heap-buffer-overflow" in bad.stderr
+    # (the word is read four bytes at a time: whichever of its eight reads is reported lies 0 .. 28 bytes behind the state)
+    assert re.search(r"READ of size 4 .*\n(.*\n)*.* is located (0|4|8|12|16|20|24|28) bytes (after|to the right of) 160-byte region",
+                     bad.stderr)

@@ -1,5 +1,5 @@
-"""CPU tier: the shipped permutation kernels -- k_perm_fast, k_perm_coop, k_states_literal, both traces, the scaled trace
-and the witness -- compiled for the host from the unchanged sources and run through the shipped launch policy under
+"""CPU tier: the shipped permutation kernels -- k_perm_fast, k_perm_coop, k_perm_lanes (helped and not), k_perm_rows,
+k_states_literal, both traces, the scaled trace and the witness -- compiled for the host from the unchanged sources and run through the shipped launch policy under
 ASan+UBSan (tests/hostsim_lib.py), byte for byte against the oracle.  Buffers are heap blocks of exactly their size, so a
 read or write past byte n is a sanitizer report; the dynamic LDS behind a launch's request is poisoned.
 
@@ -20,7 +20,7 @@ import hades_spec as S  # noqa: E402
 import hostsim_lib as HS  # noqa: E402
 import oracle_lib  # noqa: E402
 from oracle_lib import limbs_of, int_of  # noqa: E402
-from gpu_common import EDGE_VALUES, edge_scalars, catalogue_states, placed_batches, WIRES  # noqa: E402
+from gpu_common import EDGE_VALUES, edge_scalars, catalogue_states, placed_batches, WIRES, FORM_SIZES  # noqa: E402
 
 LITERAL, FAST, COOP = 1, 2, 3
 SELECTORS = {"fast": FAST, "coop": COOP, "literal": LITERAL}
@@ -112,14 +112,54 @@ def test_default_dispatch_past_coop_threshold(oracle):
     assert (u64(r.out["st"]) == oracle.perm_batch(inp)).all()
 
 
-def test_default_dispatch_small_batch_is_not_emulated():
-    """Up to 4 096 states the size rule picks the DPP forms of hades_lanes.hpp: the stand-in ends the run with a clear message
-    instead of computing something else."""
+# ---- the latency forms of hades_lanes.hpp: DPP row moves and permlane swaps emulated by the stand-in header ---------------
+# One emulated block of four waves costs seconds (two wave barriers per DPP move, ~13 000 moves per permutation), so the
+# sizes are the smallest that reach every role of a block.  form: tests/hostsim/hostsim_main.cpp, namespace forms.
+LANES, ROWS = 4, 5
+HELPED, UNHELPED, PER_ROW = 0, 1, 2
+
+
+def test_default_dispatch_single_permutation_runs_the_helped_lanes_form(kat):
+    """The reference's real call shape, ONE permutation, through the default dispatch: k_perm_lanes<true>, a lone state
+    wave and its helper.  Known answers, one call each."""
+    assert FORM_SIZES["lanes_helped"][0] == 1
+    inp = np.array([l for s in kat["single"] for x in s["in_mont"] for l in limbs_of(int(x, 16))], dtype=np.uint64)
+    exp = np.array([l for s in kat["single"] for x in s["out_mont"] for l in limbs_of(int(x, 16))], dtype=np.uint64)
+    n = 3                                                # (all eleven, as one batch: tests/test_hostsim_mutants.py's unchanged run)
     s = HS.Script()
-    s.zero("st", 160)
-    s.call("hades252_perm_batch_dev", "st", 1, None)
-    r = s.run(timeout=60, check=False)
-    assert r.returncode != 0 and "form not emulated" in r.stderr
+    s.call("hades252_kernel_for", 1)
+    for i in range(n):
+        s.buf("one%d" % i, inp[20 * i:20 * i + 20].tobytes())
+        s.call("hades252_perm_batch_dev", "one%d" % i, 1, None)
+        s.dump("one%d" % i)
+    r = s.run(timeout=600)                               # measured: 2.2 s per known answer
+    assert r.rc == [("hades252_kernel_for", LANES)] + [("hades252_perm_batch_dev", 0)] * n
+    assert "not_emulated" not in r.stdout
+    for i in range(n):
+        assert (u64(r.out["one%d" % i]) == exp[20 * i:20 * i + 20]).all(), i
+
+
+@pytest.mark.parametrize("form,n", [(HELPED, 3), (HELPED, 4), (UNHELPED, 5), (PER_ROW, 4), (PER_ROW, 5)],
+                         ids=["helped-full_block", "helped-ragged_block_idle_waves", "unhelped-full_and_ragged_block",
+                              "rows-one_full_wave", "rows-ragged_second_wave"])
+def test_lanes_and_rows_forms_in_place_edge_values(oracle, form, n):
+    """k_perm_lanes<true> (three state waves and the helper; then a second block with one state wave, two idle waves and
+    the helper), k_perm_lanes<false> (four state waves; then a block whose other waves return at once) and k_perm_rows (one
+    state per 16-lane row: a full wave, then a wave with one row in use) on exact-size buffers of edge values.  The helped
+    form and the rows form go through the shipped selector; the unhelped form belongs to 769 .. 1 024 states, which the
+    emulation cannot afford, and is launched with its call site's geometry by form_perm."""
+    assert n < FORM_SIZES["lanes"][0] < FORM_SIZES["rows"][0]
+    inp = states_of(n, 4000 + 10 * form + n)
+    s = HS.Script()
+    s.buf("st", inp.tobytes())
+    if form == UNHELPED:
+        s.call("form_perm", "st", n, UNHELPED)
+    else:
+        s.call("hades252_perm_batch_dev_ex", "st", n, None, LANES if form == HELPED else ROWS)
+    s.dump("st")
+    r = s.run(timeout=600)                               # measured: 5.5 / 7.1 s (helped), 8.2 s (unhelped), 3.0 / 5.0 s (rows)
+    assert [rc for _, rc in r.rc] == [0] and "not_emulated" not in r.stdout
+    assert (u64(r.out["st"]) == oracle.perm_batch(inp)).all()
 
 
 @pytest.mark.parametrize("name", list(SELECTORS))

@@ -61,7 +61,7 @@ def test_perm_fast_coop_and_the_traces(oracle):
 
 def test_fused_merkle_coop_launch(oracle, monkeypatch):
     """The two-level k_merkle_coop launch of merkle_run (arity 2, 2^15 leaves): level 1 stays in LDS for level 2."""
-    monkeypatch.setenv("HOSTSIM_SKIP_NOT_EMULATED", "1")
+    monkeypatch.setenv("HOSTSIM_DPP_MAX_BLOCKS", "0")
     leaves = edge_scalars(1 << 15, 601)
     levels = oracle.merkle_tree(leaves, 2, TAG[2], 1)
     tree_bytes = 8 * sum(l.size for l in levels)
@@ -110,3 +110,62 @@ def test_sponge_sort_per_lane_sponge_and_cipher(oracle):
     assert (u64(r.out["dig"]) == oracle.sponge_var(pool, offs, lens, CAP, 1)).all()
     exp_c = CM.encrypt_batch(msgs.reshape(nc, m, 4), keys.reshape(nc, 2, 4), nonces.reshape(nc, 4), m, oracle.perm_batch)
     assert (u64(r.out["c"]).reshape(exp_c.shape) == exp_c).all()
+
+
+# ---- the DPP forms of hades_lanes.hpp: where waves meet through LDS -----------------------------------------------------
+# The helped form's main waves and helper wave exchange word 3 through LanesLds::xw with one block barrier per full round;
+# every DPP move is a wave-wide exchange in the emulator, so what TSan orders by is the barriers the SOURCE has
+# (tests/test_hostsim_mutants.py puts both sides on one buffer to prove the detector live).
+LANES, ROWS = 4, 5
+
+
+def test_perm_lanes_helped_and_rows(oracle):
+    """k_perm_lanes<true>, four states: a full block, then a block with one state wave, two idle waves and the helper;
+    k_perm_rows, five states (rows never meet: the wave's own LDS round trips only)."""
+    assert FORM_SIZES["lanes_helped"][0] <= 4 < FORM_SIZES["lanes"][0]
+    s = HS.Script("perm", "tsan")
+    inp = {}
+    for name, n, k in (("lanes", 4, LANES), ("rows", 5, ROWS)):
+        inp[name] = edge_scalars(5 * n, 610 + n)
+        s.buf(name, inp[name].tobytes())
+        s.call("hades252_perm_batch_dev_ex", name, n, None, k)
+        s.dump(name)
+    r = s.run(timeout=900)                               # measured: 9 s + 7 s
+    assert [rc for _, rc in r.rc] == [0, 0]
+    for name in inp:
+        assert (u64(r.out[name]) == oracle.perm_batch(inp[name])).all(), name
+
+
+def test_sponge_and_duplex_sponge_lanes_helped(oracle):
+    """k_sponge_lanes<true> on four ragged messages (the waves of a block run to the block's maximum) and
+    k_safe_lanes<true> on four sponges, one-shot: several permutations per launch, so the buffers of one permutation's last
+    rounds meet the next one's first."""
+    import safe_model as SM
+    import hades_spec as S
+    n = 4
+    lens = [5, 2, 0, 3]
+    pool = edge_scalars(sum(lens), 620)
+    offs, la = np.cumsum([0] + lens[:-1]).astype(np.uint64), np.array(lens, dtype=np.uint64)
+    s = HS.Script("sponge", "tsan")
+    s.buf("pool", pool.tobytes())
+    s.buf("offs", offs.tobytes())
+    s.buf("lens", la.tobytes())
+    s.buf("cap", limbs(CAP))
+    s.fill("dig", 32 * n, 0xFF)
+    s.zero("bad", 4)
+    s.call("hades252_sponge_hash_var_dev", "pool", sum(lens), "offs", "lens", n, "cap", 1, "dig", "bad", None)
+    s.dump("dig")
+    pat = [SM.A(5), SM.Q(1)]
+    tag = S.to_mont(0x1234)
+    inp = edge_scalars(n * 5, 621).reshape(n, 5, 4)
+    s.buf("tag", limbs(tag))
+    s.buf("in", inp.tobytes())
+    s.buf("calls", np.array(SM.encode(pat), dtype=np.uint32).tobytes())
+    s.fill("out", 32 * n, 0xFF)
+    s.call("hades252_safe_hash_dev", "in", n, "calls", len(pat), "tag", "out", None)
+    s.dump("out")
+    r = s.run(timeout=1200)                              # measured: 40 s
+    assert [rc for _, rc in r.rc] == [0, 0]
+    assert (u64(r.out["dig"]) == oracle.sponge_var(pool, offs, la, CAP, 1)).all()
+    want = SM.run_batch(pat, inp, tag, oracle.perm_batch)
+    assert (u64(r.out["out"]).reshape(want.shape) == want).all()

@@ -1,5 +1,6 @@
-"""CPU tier: every per-lane field routine that tests/units/arith_units.hip wraps (all but the DPP ones, units_lane_* and
-carry_split), run from the unchanged headers in the host build under ASan+UBSan.
+"""CPU tier: every field routine that tests/units/arith_units.hip wraps -- the per-lane ones, the lane-split ones of
+hades_lanes.hpp (units_lane_*, carry_split) and the DPP / permlane moves those are made of -- run from the unchanged headers
+in the host build under ASan+UBSan.
 
 The test bodies are those of tests/test_gpu_a13_units.py themselves -- the same operands (the adversarial maximal-limb
 operands of tests/test_fast_model.py among them), the same Python models, the same assertions -- called with a stand-in
@@ -158,9 +159,40 @@ def test_fr_add_and_mul_vs_truth(host):
     U.test_fr_add_and_mul_vs_truth(*host)
 
 
-def test_every_wrapped_routine_but_the_dpp_ones_is_driven():
-    """The launchers of arith_units.hip that this file does not reach are exactly the DPP ones."""
+# ---- hades_lanes.hpp: the stand-in header emulates the DPP row moves and the permlane swaps (one wave-wide exchange each)
+def test_dpp_moves_vs_model(host):
+    """The emulation itself, held to the model the MI355X is held to by the GPU tier's run of the same body."""
+    U.test_dpp_moves_vs_model(*host)
+
+
+@pytest.fixture()
+def fewer_randoms(monkeypatch):
+    """A launch of the lane routines costs two wave barriers per DPP move here: 64 random rows (plus four per mixed wave)
+    instead of the GPU tier's 512 to 1 024; every adversarial pattern, and every pair of them, stays."""
+    monkeypatch.setattr(U, "N_RANDOM", 256)
+
+
+def test_lane_mont_mul_and_sbox_vs_model(host, fewer_randoms):
+    U.test_lane_mont_mul_and_sbox_vs_model(*host)
+
+
+def test_lane_lin_vs_model(host, fewer_randoms):
+    U.test_lane_lin_vs_model(*host)
+
+
+def test_lane_mds_row_vs_model(host, fewer_randoms):
+    U.test_lane_mds_row_vs_model(*host)
+
+
+def test_carry_split_vs_model(host, fewer_randoms):
+    U.test_carry_split_vs_model(*host)
+
+
+def test_every_wrapped_routine_is_driven():
+    """No launcher of arith_units.hip is out of this tier's reach, and this file has a test for each body of the GPU tier."""
     import units_lib
     reached = set(HS.entry_points("perm"))
     missing = {n for n in list(units_lib._PTRS) + ["units_mds_row_cols", "units_lane_mds_row"] if n not in reached}
-    assert missing == {"units_lane_mont_mul", "units_lane_sbox", "units_lane_lin", "units_lane_mds_row", "units_carry_split"}
+    assert missing == set()
+    bodies = {n for n in dir(U) if n.startswith("test_")}
+    assert bodies <= set(globals()), bodies - set(globals())

@@ -11,7 +11,8 @@ import units_lib  # noqa: E402
 
 WRAPPED = ["to_f29", "from_f29", "mont_fips", "mont_mul_small", "mont_lin", "mont_lin1", "sbox29", "add_lazy", "small_mds",
            "finalize", "finalize1", "finalize32", "mds_row_cols", "fr_add", "fr_cond_sub_p", "fr_mul", "fr_is_canonical",
-           "lane_mont_mul", "lane_lin", "lane_sbox", "lane_mds_row", "carry_split"]
+           "lane_mont_mul", "lane_lin", "lane_sbox", "lane_mds_row", "carry_split", "row_shr", "row_shl", "row_bcast",
+           "wave_bcast_row"]
 HEADERS = ["fr32.hpp", "hades_constants.inc", "hades_literal.hpp", "staging.hpp", "hades_fast.hpp", "k_perm_fast.hpp",
            "hades_coop.hpp", "hades_lanes.hpp", "device_tables.hpp", "kernels_perm.hpp"]
 

@@ -219,6 +219,37 @@ __global__ void u_carry_split(const uint64_t *acc, uint32_t *t, uint32_t *c16, u
     c17[16 * r + k] = b;
 }
 
+// ---- hades_lanes.hpp: the data moves themselves, one element per WAVE (64 lanes in, kDppMoves x 64 lanes out) --------
+// results, 64 words each: row_shr<1..15>, row_shl<1..15>, row_bcast<0..15>, wave_bcast_row<0>, <1>, then both halves of
+// v_permlane16_swap a, b and of v_permlane32_swap a, b (the raw builtins wave_bcast_row is made of, with d != s)
+constexpr int kDppMoves = 52;
+template <int N>
+__device__ __forceinline__ void row_moves(uint32_t v, uint32_t *o) {
+    if constexpr (N < 16) {
+        if constexpr (N > 0) {
+            o[64 * (N - 1)] = row_shr<N>(v);
+            o[64 * (14 + N)] = row_shl<N>(v);
+        }
+        o[64 * (30 + N)] = row_bcast<N>(v);
+        row_moves<N + 1>(v, o);
+    }
+}
+__global__ void u_dpp_moves(const uint32_t *a, const uint32_t *b, uint32_t *out, size_t n) {
+    const size_t t = elem(), w = t >> 6;                             // a wave is wholly in or wholly out of range
+    if (w >= n) return;
+    const uint32_t va = a[t], vb = b[t];
+    uint32_t *o = out + w * (64 * kDppMoves) + (threadIdx.x & 63);
+    row_moves<0>(va, o);
+    o[64 * 46] = wave_bcast_row<0>(va);
+    o[64 * 47] = wave_bcast_row<1>(va);
+    const auto h = __builtin_amdgcn_permlane16_swap(va, vb, false, false);
+    o[64 * 48] = h[0];
+    o[64 * 49] = h[1];
+    const auto q = __builtin_amdgcn_permlane32_swap(va, vb, false, false);
+    o[64 * 50] = q[0];
+    o[64 * 51] = q[1];
+}
+
 dim3 grid_for(size_t threads) { return dim3((unsigned)((threads + kUnitBlock - 1) / kUnitBlock)); }
 
 int status() { return hipGetLastError() == hipSuccess ? 0 : -1; }
@@ -312,6 +343,9 @@ int units_lane_mds_row(const void *x, int row, void *out, size_t n, void *stream
 }
 int units_carry_split(const void *acc, void *t, void *c16, void *c17, size_t n, void *stream) {
     UNITS_LAUNCH(u_carry_split, 16 * n, (const uint64_t *)acc, (uint32_t *)t, (uint32_t *)c16, (uint32_t *)c17, n);
+}
+int units_dpp_moves(const void *a, const void *b, void *out, size_t n, void *stream) {
+    UNITS_LAUNCH(u_dpp_moves, 64 * n, (const uint32_t *)a, (const uint32_t *)b, (uint32_t *)out, n);
 }
 
 }  // extern "C"

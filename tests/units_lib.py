@@ -20,7 +20,7 @@ _PTRS = {"units_to_f29": 2, "units_from_f29": 2, "units_mont_mul": 3, "units_mon
          "units_mont_mul_small": 3, "units_mont_lin": 3, "units_mont_lin1": 3, "units_sbox29": 2, "units_add_lazy": 3,
          "units_small_mds": 2, "units_finalize": 2, "units_finalize1": 2, "units_finalize32": 2, "units_fr_add": 3,
          "units_fr_cond_sub_p": 3, "units_fr_mul": 3, "units_fr_is_canonical": 2, "units_lane_mont_mul": 3,
-         "units_lane_sbox": 2, "units_lane_lin": 3, "units_carry_split": 4}
+         "units_lane_sbox": 2, "units_lane_lin": 3, "units_carry_split": 4, "units_dpp_moves": 3}
 _VP, _SZ, _I = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
 
 
