@@ -29,6 +29,7 @@ CIPHER_MAX_LEN = 1024
 SAFE_MAX_CALLS = 64
 SAFE_MAX_WORDS = 1 << 20
 SAFE_ABSORB = 1 << 31
+GRIND_MAX_JOBS = 65535
 
 # every symbol include/hades252.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -153,6 +154,7 @@ SIGNATURES = {
                                                  c_void_p, c_size_t, POINTER(c_size_t), c_void_p]),
     "hades252_safe_squeeze_witness_dev": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, POINTER(ctypes.c_uint32), c_void_p,
                                                   c_void_p, c_size_t, POINTER(c_size_t), c_void_p]),
+    "hades252_grind": (c_int, [c_void_p, c_size_t, c_int, c_int, POINTER(c_uint64), c_uint64, c_uint64, c_void_p, c_void_p]),
     "hades252_gen_b_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_uint64, c_void_p]),
     "hades252_gen_a_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_void_p]),
     "hades252_digest_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_void_p, c_void_p]),

@@ -36,7 +36,11 @@ LAUNCH_POLICY_DEPS = ["launch.hpp", "abi_perm.hpp", "abi_merkle.hpp", "abi_spong
 UNRECORDED_KERNEL_DEPS = ["kernels_cipher.hpp", "abi_cipher.hpp", "kernels_safe.hpp", "abi_safe.hpp", "kernels_witness.hpp", "abi_witness.hpp"]
 # host plumbing (error / fault hook, page-locked memory, pipe pool, chunk pipeline, one-shot host callers, generators)
 HOST_DEPS = ["hades252.hip", "host_fault.hpp", "abi_util.hpp", "host_pin.hpp", "host_pool.hpp", "host_pipe.hpp", "host_callers.hpp", "host_cipher.hpp", "host_safe.hpp"]
-DEPS = HOST_DEPS + LAUNCH_POLICY_DEPS + DEVICE_DEPS + UNRECORDED_KERNEL_DEPS + [os.path.join("..", "..", "include", "hades252.h")]
+# proof-of-work grinding: a kernel and its host loop that the host simulation does not run yet (its driver includes every file
+# of the three lists above, and would have to change), and that no committed counter record covers: rebuilt like every other
+# source (DEPS), outside device_source_hash and perm_fast_hash
+GRIND_DEPS = ["kernels_grind.hpp", "host_grind.hpp"]
+DEPS = HOST_DEPS + LAUNCH_POLICY_DEPS + DEVICE_DEPS + UNRECORDED_KERNEL_DEPS + GRIND_DEPS + [os.path.join("..", "..", "include", "hades252.h")]
 # what the dominant kernel (k_perm_fast) is made of: profiles recorded for it stay valid while these are unchanged
 PERM_FAST_DEPS = ["fr32.hpp", "staging.hpp", "hades_fast.hpp", "k_perm_fast.hpp"]
 # ... plus these tables of hades_constants.inc (other kernels' tables may change without touching k_perm_fast)

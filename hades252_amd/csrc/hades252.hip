@@ -33,6 +33,7 @@ using namespace hades;
 #include "kernels_sponge.hpp"
 #include "kernels_cipher.hpp"
 #include "kernels_safe.hpp"
+#include "kernels_grind.hpp"
 #include "kernels_witness.hpp"
 #include "kernels_aux.hpp"
 
@@ -54,4 +55,5 @@ using namespace hades;
 #include "host_pipe.hpp"
 #include "host_callers.hpp"
 #include "host_safe.hpp"
+#include "host_grind.hpp"
 #include "host_cipher.hpp"

@@ -1166,6 +1166,42 @@ class SafeWitnessSponge(SafeSponge):
         return self._records(self._inputs)
 
 
+# ---- proof-of-work grinding (include/hades252.h, CONVENTION UNPINNED: tests/grind_model.py) -----------------------------
+def grind_target(bits: int) -> int:
+    """The target that asks for `bits` bits of work: p >> bits (a digest is uniform below p, so one nonce in 2^bits hits)."""
+    if not isinstance(bits, int) or bits < 0:
+        raise ValueError("grind_target: bits must be a non-negative integer, got %r" % (bits,))
+    return _FR_P >> bits
+
+
+def grind(seeds: np.ndarray, word: int, out_idx: int, target: int, first_nonce: int = 0, max_nonces: int = 1 << 32):
+    """``hades252_grind``: per job (seeds[j]: five scalars, Montgomery limbs, HOST numpy uint64 [n, 5, 4]) the smallest nonce
+    x in [first_nonce, first_nonce + max_nonces) for which word ``out_idx`` of perm(seed with seed[word] + x) is, as a
+    canonical integer, strictly below ``target`` (a Python int below 2^256).  -> (nonces uint64 [n], found bool [n]);
+    nonces[j] is 0 where found[j] is False."""
+    if not isinstance(seeds, np.ndarray) or seeds.dtype != np.uint64 or not seeds.flags["C_CONTIGUOUS"]:
+        raise TypeError("grind: seeds must be a C-contiguous numpy uint64 array")
+    if seeds.ndim != 3 or seeds.shape[1:] != (WIDTH, 4):
+        raise ValueError("grind: seeds must have shape [n, %d, 4], got %r" % (WIDTH, seeds.shape))
+    for name, v in (("word", word), ("out_idx", out_idx)):
+        if not isinstance(v, int) or not 0 <= v < WIDTH:
+            raise ValueError("grind: %s must be 0 .. %d, got %r" % (name, WIDTH - 1, v))
+    if not isinstance(target, int) or not 0 <= target < 1 << 256:
+        raise ValueError("grind: the target is an integer in [0, 2^256), got %r" % (target,))
+    if not isinstance(first_nonce, int) or not isinstance(max_nonces, int) or first_nonce < 0 or max_nonces < 0 or \
+            first_nonce + max_nonces > 1 << 64 or max_nonces >= 1 << 64:
+        raise ValueError("grind: the nonce range [%r, %r + %r) does not lie in [0, 2^64)" % (first_nonce, first_nonce, max_nonces))
+    n = seeds.shape[0]
+    if n > _lib.GRIND_MAX_JOBS:
+        raise ValueError("grind: at most %d jobs per call, got %d" % (_lib.GRIND_MAX_JOBS, n))
+    nonces = np.zeros(n, dtype=np.uint64)
+    found = np.zeros(n, dtype=np.uint8)
+    tgt = (ctypes.c_uint64 * 4)(*[(target >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(4)])
+    check(_lib.lib().hades252_grind(_ptr(seeds), n, word, out_idx, tgt, first_nonce, max_nonces, _ptr(nonces), _ptr(found)),
+          "grind")
+    return nonces, found.astype(bool)
+
+
 GEN_SEED = 0x4861646573323532
 
 

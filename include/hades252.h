@@ -583,6 +583,31 @@ int hades252_safe_absorb_witness_dev(void *d_states, size_t n_states, const void
 int hades252_safe_squeeze_witness_dev(void *d_states, size_t n_states, size_t len, void *d_out, uint32_t *cursor,
                                       void *d_inputs, void *d_wires, size_t total_steps, size_t *step, void *stream);
 
+/* ---- batched proof-of-work grinding over the permutation (f10) ---- CONVENTION UNPINNED
+ * The search a Fiat-Shamir grind, a rate-limiting puzzle or a proof of work over a Poseidon transcript needs: the smallest
+ * nonce whose digest is below a target.  Nothing in the reference tree defines a proof of work: the definition is this
+ * repository's own and pinned only to its model (tests/grind_model.py).  A job is a seed state of five scalars.  For a
+ * nonce x < 2^64
+ *   candidate(x) = the seed with word `word` replaced by seed[word] + x (mod p)
+ *   digest(x)    = the canonical integer (what hades252_to_bytes_dev gives, NOT the Montgomery limbs) of word `out_idx` of
+ *                  perm(candidate(x))
+ *   x is a hit  <=>  digest(x) < target, strictly.  target is any 256-bit integer: 0 never hits, anything >= p hits at once.
+ * The answer of job j is the SMALLEST hit in [first_nonce, first_nonce + max_nonces): found[j] = 1 and nonces[j] = that
+ * nonce, or found[j] = 0 and nonces[j] left untouched.  It is a pure function of the arguments: it does not depend on grid
+ * sizes, launch windows, early exits or dispatch order.  All jobs of a call share word, out_idx, target and the range.
+ * In sponge terms (both sponges add an absorbed word into a rate word) a candidate is one absorb of x into word `word` of a
+ * resident state, one permutation and one word read: hades252_sponge_absorb_dev / hades252_sponge_squeeze_dev verify a nonce.
+ * Host memory in and out (a job is 160 bytes in and 9 out: there is no device-pointer form).  seeds: n_jobs x 5 x 4
+ * Montgomery limbs, fully reduced (not checked, as for perm); target: 4 limbs, little-endian, the plain integer.  The
+ * search runs in rounds of one launch each; after a round 8 bytes per job come back, and it stops when every job is found
+ * or the range is exhausted.
+ * Rules, all decided before the device is touched: n_jobs = 0 is a no-op success; a NULL seeds, target, nonces or found,
+ * word or out_idx outside 0 .. 4, n_jobs > HADES252_GRIND_MAX_JOBS (the job is a grid dimension) or first_nonce + max_nonces
+ * > 2^64 is HADES252_ERR_INVALID_ARG; max_nonces = 0 sets every found[j] = 0 and succeeds without a device. */
+#define HADES252_GRIND_MAX_JOBS 65535
+int hades252_grind(const uint64_t *seeds, size_t n_jobs, int word, int out_idx, const uint64_t target[4], uint64_t first_nonce,
+                   uint64_t max_nonces, uint64_t *nonces, uint8_t *found);
+
 /* ---- synthetic inputs and digests (benchmark / verification plumbing) --------------------- */
 /* Generator B: scalar e (global element index first_elem + k) gets 4 splitmix64 limbs, top limb
  * masked to 62 bits (always < p); see DESIGN.md.  Stateless, so shards generate independently. */

@@ -226,6 +226,15 @@ inline void safe_hash(const BlsScalar *in, std::size_t n_msgs, const std::uint32
     check(hades252_safe_hash(reinterpret_cast<const std::uint64_t *>(in), n_msgs, calls, n_calls, tag.limbs,
                              reinterpret_cast<std::uint64_t *>(out)), "safe_hash");
 }
+// Proof-of-work grinding, host memory (include/hades252.h, CONVENTION UNPINNED: tests/grind_model.py): per job (a seed of five
+// scalars) the smallest nonce x in [first_nonce, first_nonce + max_nonces) for which word out_idx of perm(seed with
+// seed[word] + x) is, as a canonical integer, strictly below `target` (4 limbs, little-endian, NOT Montgomery).
+// found[j] = 1 and nonces[j] = the nonce, or found[j] = 0 and nonces[j] untouched.
+inline void grind(const BlsScalar *seeds, std::size_t n_jobs, int word, int out_idx, const std::uint64_t target[4],
+                  std::uint64_t first_nonce, std::uint64_t max_nonces, std::uint64_t *nonces, std::uint8_t *found) {
+    check(hades252_grind(reinterpret_cast<const std::uint64_t *>(seeds), n_jobs, word, out_idx, target, first_nonce, max_nonces,
+                         nonces, found), "grind");
+}
 // DEVICE memory, enqueued on `stream`: the whole pattern in one launch, or call by call on the 160-byte states of
 // hades252_sponge_init_dev with a caller-owned cursor (0 = fresh) that moves with every call.
 inline void safe_hash_dev(const void *d_in, std::size_t n_msgs, const std::uint32_t *calls, std::size_t n_calls,
