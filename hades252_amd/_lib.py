@@ -155,6 +155,9 @@ SIGNATURES = {
     "hades252_safe_squeeze_witness_dev": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, POINTER(ctypes.c_uint32), c_void_p,
                                                   c_void_p, c_size_t, POINTER(c_size_t), c_void_p]),
     "hades252_grind": (c_int, [c_void_p, c_size_t, c_int, c_int, POINTER(c_uint64), c_uint64, c_uint64, c_void_p, c_void_p]),
+    "hades252_perm_inverse_batch": (c_int, [c_void_p, c_size_t]),
+    "hades252_perm_inverse_rounds": (c_int, [c_void_p, c_size_t, c_int, c_int]),
+    "hades252_fifth_root_batch": (c_int, [c_void_p, c_size_t]),
     "hades252_gen_b_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_uint64, c_void_p]),
     "hades252_gen_a_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_void_p]),
     "hades252_digest_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_void_p, c_void_p]),

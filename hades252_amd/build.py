@@ -40,7 +40,11 @@ HOST_DEPS = ["hades252.hip", "host_fault.hpp", "abi_util.hpp", "host_pin.hpp", "
 # of the three lists above, and would have to change), and that no committed counter record covers: rebuilt like every other
 # source (DEPS), outside device_source_hash and perm_fast_hash
 GRIND_DEPS = ["kernels_grind.hpp", "host_grind.hpp"]
-DEPS = HOST_DEPS + LAUNCH_POLICY_DEPS + DEVICE_DEPS + UNRECORDED_KERNEL_DEPS + GRIND_DEPS + [os.path.join("..", "..", "include", "hades252.h")]
+# the inverse permutation and the fifth roots: kernels, their generated tables and their host loop, host pointers only.  No
+# committed counter record covers them and no other kernel includes them: rebuilt like every other source (DEPS), outside
+# device_source_hash and perm_fast_hash.  The host simulation runs them from a driver of their own (tests/hostsim_inverse).
+INVERSE_DEPS = ["kernels_inverse.hpp", "hades_inverse_constants.inc", "host_inverse.hpp"]
+DEPS = HOST_DEPS + LAUNCH_POLICY_DEPS + DEVICE_DEPS + UNRECORDED_KERNEL_DEPS + GRIND_DEPS + INVERSE_DEPS + [os.path.join("..", "..", "include", "hades252.h")]
 # what the dominant kernel (k_perm_fast) is made of: profiles recorded for it stay valid while these are unchanged
 PERM_FAST_DEPS = ["fr32.hpp", "staging.hpp", "hades_fast.hpp", "k_perm_fast.hpp"]
 # ... plus these tables of hades_constants.inc (other kernels' tables may change without touching k_perm_fast)

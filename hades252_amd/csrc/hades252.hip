@@ -34,6 +34,8 @@ using namespace hades;
 #include "kernels_cipher.hpp"
 #include "kernels_safe.hpp"
 #include "kernels_grind.hpp"
+#include "hades_inverse_constants.inc"
+#include "kernels_inverse.hpp"
 #include "kernels_witness.hpp"
 #include "kernels_aux.hpp"
 
@@ -56,4 +58,5 @@ using namespace hades;
 #include "host_callers.hpp"
 #include "host_safe.hpp"
 #include "host_grind.hpp"
+#include "host_inverse.hpp"
 #include "host_cipher.hpp"

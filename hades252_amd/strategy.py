@@ -1202,6 +1202,48 @@ def grind(seeds: np.ndarray, word: int, out_idx: int, target: int, first_nonce: 
     return nonces, found.astype(bool)
 
 
+ROUNDS_TOTAL = TOTAL_FULL_ROUNDS + PARTIAL_ROUNDS          # HADES252_ROUNDS_TOTAL
+
+
+def _inverse_input(where: str, a, tail: tuple) -> np.ndarray:
+    """Type, contiguity and shape of a host batch, as grind checks its seeds; -> a copy the library works on in place."""
+    if not isinstance(a, np.ndarray) or a.dtype != np.uint64 or not a.flags["C_CONTIGUOUS"]:
+        raise TypeError("%s: the input must be a C-contiguous numpy uint64 array" % where)
+    if a.ndim != 1 + len(tail) or a.shape[1:] != tail:
+        raise ValueError("%s: the input must have shape [n, %s], got %r" % (where, ", ".join(map(str, tail)), a.shape))
+    return a.copy()
+
+
+def perm_inverse_rounds(states: np.ndarray, round_hi: int, round_lo: int) -> np.ndarray:
+    """``hades252_perm_inverse_rounds``: rounds round_hi - 1, ..., round_lo of the permutation undone on HOST numpy uint64
+    states [n, 5, 4] (Montgomery limbs): the state after round round_hi - 1 in, the state after round round_lo - 1 (the
+    permutation's input for round_lo = 0) out, as a new array."""
+    out = _inverse_input("perm_inverse_rounds", states, (WIDTH, 4))
+    for v in (round_hi, round_lo):
+        if not isinstance(v, int) or isinstance(v, bool):
+            raise ValueError("perm_inverse_rounds: a round number is an int, got %r" % (v,))
+    if not 0 <= round_lo <= round_hi <= ROUNDS_TOTAL:
+        raise ValueError("perm_inverse_rounds: 0 <= round_lo <= round_hi <= %d, got (%r, %r)" % (ROUNDS_TOTAL, round_hi, round_lo))
+    check(_lib.lib().hades252_perm_inverse_rounds(_ptr(out), out.shape[0], round_hi, round_lo), "perm_inverse_rounds")
+    return out
+
+
+def perm_inverse(states: np.ndarray) -> np.ndarray:
+    """``hades252_perm_inverse_batch``: the preimages of HOST numpy uint64 states [n, 5, 4] under the permutation, as a new
+    array: perm(perm_inverse(y)) == y."""
+    out = _inverse_input("perm_inverse", states, (WIDTH, 4))
+    check(_lib.lib().hades252_perm_inverse_batch(_ptr(out), out.shape[0]), "perm_inverse")
+    return out
+
+
+def fifth_root(scalars: np.ndarray) -> np.ndarray:
+    """``hades252_fifth_root_batch``: x -> x^(1/5) on HOST numpy uint64 scalars [n, 4] (Montgomery limbs), as a new array: the
+    inverse of quintic_s_box on independent scalars."""
+    out = _inverse_input("fifth_root", scalars, (4,))
+    check(_lib.lib().hades252_fifth_root_batch(_ptr(out), out.shape[0]), "fifth_root")
+    return out
+
+
 GEN_SEED = 0x4861646573323532
 
 

@@ -608,6 +608,34 @@ int hades252_safe_squeeze_witness_dev(void *d_states, size_t n_states, size_t le
 int hades252_grind(const uint64_t *seeds, size_t n_jobs, int word, int out_idx, const uint64_t target[4], uint64_t first_nonce,
                    uint64_t max_nonces, uint64_t *nonces, uint8_t *found);
 
+/* ---- the inverse permutation and batched fifth roots (f11) ----
+ * The permutation run backwards.  Not a convention of this repository's: every round of Strategy::perm
+ * (src/strategies.rs:79-157) is a key addition, x -> x^5 on a field with gcd(5, p - 1) = 1 and an invertible Cauchy matrix,
+ * so the inverse is determined by the reference: perm_inverse(perm(x)) == x and perm(perm_inverse(y)) == y for every
+ * canonical state.  Uses: Hades as a keyed block permutation (decryption), delay functions of the Sloth / MinRoot kind (the
+ * fifth root is the slow direction, the forward call checks it), cryptanalysis and test construction.
+ *   hades252_perm_inverse_batch    n_perms states of 5 x 4 limbs, each replaced by its preimage
+ *   hades252_perm_inverse_rounds   undoes rounds round_hi - 1, ..., round_lo of the reference's schedule (rounds 0 .. 3 and
+ *                                  63 .. 66 are full): the input is the state after round round_hi - 1 (trace[round_hi - 1] of
+ *                                  hades252_perm_trace_dev), the output the state after round round_lo - 1, or the permutation's
+ *                                  input when round_lo = 0.  (HADES252_ROUNDS_TOTAL, 0) is hades252_perm_inverse_batch.  It
+ *                                  localises a disagreement to a round.
+ *   hades252_fifth_root_batch      n_scalars independent scalars, x -> x^D with D = 5^-1 mod (p - 1): the inverse of
+ *                                  hades252_quintic_s_box_dev, 0 -> 0
+ * Host memory, in place, synchronous, the in-memory format of hades252_perm_batch (Montgomery limbs, fully reduced, not
+ * checked).  Any n: the call is chunked through a pooled pipe and holds two chunks of device memory.
+ * There is no device-pointer form, no canonical-bytes form and no one-state-per-wave latency form: a state is 160 bytes each
+ * way for about 17 forward permutations of arithmetic (99 fifth roots of 311 Montgomery products each, 67 dense 5 x 5 matrix
+ * products), so the copies hide behind the kernel.  One state alone costs about 17 permutation latencies, roughly 1 ms: that
+ * figure is not measured.
+ * Rules, all decided before the device is touched: n = 0 is a no-op success, even with a NULL pointer; NULL with n > 0, a
+ * pointer that is not 8-byte aligned, or a round range outside 0 <= round_lo <= round_hi <= HADES252_ROUNDS_TOTAL is
+ * HADES252_ERR_INVALID_ARG; round_hi == round_lo is a no-op success. */
+#define HADES252_ROUNDS_TOTAL 67
+int hades252_perm_inverse_batch(uint64_t *states, size_t n_perms);
+int hades252_perm_inverse_rounds(uint64_t *states, size_t n_perms, int round_hi, int round_lo);
+int hades252_fifth_root_batch(uint64_t *scalars, size_t n_scalars);
+
 /* ---- synthetic inputs and digests (benchmark / verification plumbing) --------------------- */
 /* Generator B: scalar e (global element index first_elem + k) gets 4 splitmix64 limbs, top limb
  * masked to 62 bits (always < p); see DESIGN.md.  Stateless, so shards generate independently. */

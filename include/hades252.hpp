@@ -235,6 +235,19 @@ inline void grind(const BlsScalar *seeds, std::size_t n_jobs, int word, int out_
     check(hades252_grind(reinterpret_cast<const std::uint64_t *>(seeds), n_jobs, word, out_idx, target, first_nonce, max_nonces,
                          nonces, found), "grind");
 }
+// The permutation run backwards, host memory, in place (include/hades252.h): perm(perm_inverse(y)) == y.  perm_inverse_rounds
+// undoes rounds round_hi - 1, ..., round_lo only (the state after round round_hi - 1 in, the state after round round_lo - 1
+// out; 0 <= round_lo <= round_hi <= HADES252_ROUNDS_TOTAL); fifth_root is x -> x^(1/5) on independent scalars.
+inline void perm_inverse(BlsScalar *states, std::size_t n_perms) {
+    check(hades252_perm_inverse_batch(reinterpret_cast<std::uint64_t *>(states), n_perms), "perm_inverse");
+}
+inline void perm_inverse_rounds(BlsScalar *states, std::size_t n_perms, int round_hi, int round_lo) {
+    check(hades252_perm_inverse_rounds(reinterpret_cast<std::uint64_t *>(states), n_perms, round_hi, round_lo),
+          "perm_inverse_rounds");
+}
+inline void fifth_root(BlsScalar *scalars, std::size_t n_scalars) {
+    check(hades252_fifth_root_batch(reinterpret_cast<std::uint64_t *>(scalars), n_scalars), "fifth_root");
+}
 // DEVICE memory, enqueued on `stream`: the whole pattern in one launch, or call by call on the 160-byte states of
 // hades252_sponge_init_dev with a caller-owned cursor (0 = fresh) that moves with every call.
 inline void safe_hash_dev(const void *d_in, std::size_t n_msgs, const std::uint32_t *calls, std::size_t n_calls,
