@@ -30,6 +30,7 @@ SAFE_MAX_CALLS = 64
 SAFE_MAX_WORDS = 1 << 20
 SAFE_ABSORB = 1 << 31
 GRIND_MAX_JOBS = 65535
+MATRIX_MAX_COLS = 4096
 
 # every symbol include/hades252.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -158,6 +159,13 @@ SIGNATURES = {
     "hades252_perm_inverse_batch": (c_int, [c_void_p, c_size_t]),
     "hades252_perm_inverse_rounds": (c_int, [c_void_p, c_size_t, c_int, c_int]),
     "hades252_fifth_root_batch": (c_int, [c_void_p, c_size_t]),
+    "hades252_matrix_row_digests": (c_int, [c_void_p, c_size_t, c_size_t, c_size_t, POINTER(c_uint64), c_int, c_void_p]),
+    "hades252_matrix_commit": (c_int, [c_void_p, c_size_t, c_size_t, c_size_t, POINTER(c_uint64), c_int, c_int,
+                                       POINTER(c_uint64), c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hades252_matrix_open": (c_int, [c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                     c_size_t, c_void_p, c_void_p]),
+    "hades252_matrix_verify": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int, c_int, POINTER(c_uint64), c_int,
+                                       POINTER(c_uint64), c_int, c_void_p]),
     "hades252_gen_b_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_uint64, c_void_p]),
     "hades252_gen_a_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_void_p]),
     "hades252_digest_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_void_p, c_void_p]),

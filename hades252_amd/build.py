@@ -44,7 +44,12 @@ GRIND_DEPS = ["kernels_grind.hpp", "host_grind.hpp"]
 # committed counter record covers them and no other kernel includes them: rebuilt like every other source (DEPS), outside
 # device_source_hash and perm_fast_hash.  The host simulation runs them from a driver of their own (tests/hostsim_inverse).
 INVERSE_DEPS = ["kernels_inverse.hpp", "hades_inverse_constants.inc", "host_inverse.hpp"]
-DEPS = HOST_DEPS + LAUNCH_POLICY_DEPS + DEVICE_DEPS + UNRECORDED_KERNEL_DEPS + GRIND_DEPS + INVERSE_DEPS + [os.path.join("..", "..", "include", "hades252.h")]
+# matrix commitments (row hashes of a column-major matrix, the tree over them, openings, verification): one kernel and its
+# host calls, host pointers only.  No committed counter record covers them and no other kernel includes them: rebuilt like
+# every other source (DEPS), outside device_source_hash and perm_fast_hash.  The host simulation runs the kernel from a
+# driver of its own (tests/hostsim_matrix).
+MATRIX_DEPS = ["kernels_matrix.hpp", "host_matrix.hpp"]
+DEPS = HOST_DEPS + LAUNCH_POLICY_DEPS + DEVICE_DEPS + UNRECORDED_KERNEL_DEPS + GRIND_DEPS + INVERSE_DEPS + MATRIX_DEPS + [os.path.join("..", "..", "include", "hades252.h")]
 # what the dominant kernel (k_perm_fast) is made of: profiles recorded for it stay valid while these are unchanged
 PERM_FAST_DEPS = ["fr32.hpp", "staging.hpp", "hades_fast.hpp", "k_perm_fast.hpp"]
 # ... plus these tables of hades_constants.inc (other kernels' tables may change without touching k_perm_fast)

@@ -36,6 +36,7 @@ using namespace hades;
 #include "kernels_grind.hpp"
 #include "hades_inverse_constants.inc"
 #include "kernels_inverse.hpp"
+#include "kernels_matrix.hpp"
 #include "kernels_witness.hpp"
 #include "kernels_aux.hpp"
 
@@ -59,4 +60,5 @@ using namespace hades;
 #include "host_safe.hpp"
 #include "host_grind.hpp"
 #include "host_inverse.hpp"
+#include "host_matrix.hpp"
 #include "host_cipher.hpp"

@@ -1244,6 +1244,119 @@ def fifth_root(scalars: np.ndarray) -> np.ndarray:
     return out
 
 
+def _matrix_planes(where: str, planes, n_rows):
+    """Type, contiguity and shape of a column-major matrix [n_cols, plane_stride, 4]; -> (n_rows, n_cols, plane_stride)."""
+    planes = _host_u64(planes, where)
+    if planes.ndim != 3 or planes.shape[2] != 4:
+        raise ValueError("%s: planes must have shape [n_cols, plane_stride, 4], got %r" % (where, planes.shape))
+    n_cols, stride = planes.shape[0], planes.shape[1]
+    if not 1 <= n_cols <= _lib.MATRIX_MAX_COLS:
+        raise ValueError("%s: 1 .. %d columns, got %d" % (where, _lib.MATRIX_MAX_COLS, n_cols))
+    if n_rows is None:
+        n_rows = stride
+    if not isinstance(n_rows, int) or isinstance(n_rows, bool) or not 0 <= n_rows <= stride:
+        raise ValueError("%s: n_rows must be 0 .. plane_stride = %d, got %r" % (where, stride, n_rows))
+    return n_rows, n_cols, stride
+
+
+def _matrix_tree_shape(where: str, n_rows: int, arity: int):
+    """(depth, digests in the tree) of the tree over n_rows leaves, without the library."""
+    if not isinstance(arity, int) or isinstance(arity, bool) or not 2 <= arity <= 4 or n_rows < 2:
+        raise ValueError("%s: need arity 2..4 and at least 2 rows (got arity %r, %d rows)" % (where, arity, n_rows))
+    sizes = merkle_level_sizes(n_rows, arity)
+    return len(sizes), sum(sizes)
+
+
+def _matrix_modes(where: str, pad_mode, out_idx=1):
+    if pad_mode not in (0, 1) or isinstance(pad_mode, bool):
+        raise ValueError("%s: pad_mode is 0 or 1, got %r" % (where, pad_mode))
+    if not isinstance(out_idx, int) or isinstance(out_idx, bool) or not 0 <= out_idx < WIDTH:
+        raise ValueError("%s: out_idx must be 0 .. %d, got %r" % (where, WIDTH - 1, out_idx))
+
+
+def _matrix_pad(where: str, pad, depth: int):
+    if pad is None:
+        return None
+    pad = _host_u64(pad, where)
+    if pad.size != depth * 4:
+        raise ValueError("%s: the padding table needs %d digests" % (where, depth))
+    return _ptr(pad)
+
+
+def matrix_row_digests_host(planes: np.ndarray, capacity_mont: int, pad_mode: int = 1, n_rows: int | None = None) -> np.ndarray:
+    """``hades252_matrix_row_digests``: the sponge digest [n_rows, 4] of every row of a matrix held column by column in HOST
+    memory (numpy uint64 [n_cols, plane_stride, 4], Montgomery limbs; rows 0 .. n_rows - 1 of every plane, all of them by
+    default): what sponge_hash_host gives for the transposed matrix."""
+    n_rows, n_cols, stride = _matrix_planes("matrix_row_digests_host", planes, n_rows)
+    _matrix_modes("matrix_row_digests_host", pad_mode)
+    out = np.zeros((n_rows, 4), dtype=np.uint64)
+    check(_lib.lib().hades252_matrix_row_digests(_ptr(planes), n_rows, n_cols, stride, _tag_arr(capacity_mont), pad_mode,
+                                                 _ptr(out)), "matrix_row_digests_host")
+    return out
+
+
+def matrix_commit_host(planes: np.ndarray, capacity_mont: int, arity: int, tag_mont: int, pad_mode: int = 1, out_idx: int = 1,
+                       pad: np.ndarray | None = None, n_rows: int | None = None, want_digests: bool = True,
+                       want_tree: bool = True):
+    """``hades252_matrix_commit``: (digests [n_rows, 4] or None, tree [nodes, 4] or None, root [4]) of the column-major matrix
+    ``planes``: the row digests of matrix_row_digests_host under the tree merkle_build builds (``pad``: host table
+    [depth, 4] or None), in one call; the digests stay on the device in between."""
+    where = "matrix_commit_host"
+    n_rows, n_cols, stride = _matrix_planes(where, planes, n_rows)
+    depth, nodes = _matrix_tree_shape(where, n_rows, arity)
+    _matrix_modes(where, pad_mode, out_idx)
+    pptr = _matrix_pad(where, pad, depth)
+    digests = np.zeros((n_rows, 4), dtype=np.uint64) if want_digests else None
+    tree = np.zeros((nodes, 4), dtype=np.uint64) if want_tree else None
+    root = np.zeros(4, dtype=np.uint64)
+    check(_lib.lib().hades252_matrix_commit(_ptr(planes), n_rows, n_cols, stride, _tag_arr(capacity_mont), pad_mode, arity,
+                                            _tag_arr(tag_mont), out_idx, pptr, None if digests is None else _ptr(digests),
+                                            None if tree is None else _ptr(tree), _ptr(root)), where)
+    return digests, tree, root
+
+
+def matrix_open_host(planes: np.ndarray, digests: np.ndarray, tree: np.ndarray, arity: int, indices,
+                     pad: np.ndarray | None = None, n_rows: int | None = None):
+    """``hades252_matrix_open``: (rows [q, n_cols, 4], paths [q, depth, arity - 1, 4]) for the row indices ``indices`` from what
+    matrix_commit_host returned.  Plain host code: no device is touched.  An index >= n_rows gives zeros."""
+    where = "matrix_open_host"
+    n_rows, n_cols, stride = _matrix_planes(where, planes, n_rows)
+    depth, nodes = _matrix_tree_shape(where, n_rows, arity)
+    digests, tree = _host_u64(digests, where), _host_u64(tree, where)
+    if digests.size != n_rows * 4 or tree.size != nodes * 4:
+        raise ValueError("%s: need %d row digests and a tree of %d digests" % (where, n_rows, nodes))
+    pptr = _matrix_pad(where, pad, depth)
+    idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+    rows = np.zeros((idx.size, n_cols, 4), dtype=np.uint64)
+    paths = np.zeros((idx.size, depth, arity - 1, 4), dtype=np.uint64)
+    check(_lib.lib().hades252_matrix_open(_ptr(planes), n_rows, n_cols, stride, _ptr(digests), _ptr(tree), arity, pptr,
+                                          _ptr(idx), idx.size, _ptr(rows), _ptr(paths)), where)
+    return rows, paths
+
+
+def matrix_verify_host(rows: np.ndarray, indices, paths: np.ndarray, arity: int, capacity_mont: int, tag_mont: int,
+                       pad_mode: int = 1, out_idx: int = 1) -> np.ndarray:
+    """``hades252_matrix_verify``: roots [q, 4] recomputed from opened rows [q, n_cols, 4], their indices and their paths
+    [q, depth, arity - 1, 4] (what matrix_open_host returns); the caller compares them with the committed root."""
+    where = "matrix_verify_host"
+    rows, paths = _host_u64(rows, where), _host_u64(paths, where)
+    if not isinstance(arity, int) or isinstance(arity, bool) or not 2 <= arity <= 4:
+        raise ValueError("%s: arity 2..4, got %r" % (where, arity))
+    if rows.ndim != 3 or rows.shape[2] != 4 or not 1 <= rows.shape[1] <= _lib.MATRIX_MAX_COLS:
+        raise ValueError("%s: rows must have shape [q, n_cols, 4], got %r" % (where, rows.shape))
+    q = rows.shape[0]
+    if paths.ndim != 4 or paths.shape[0] != q or paths.shape[1] < 1 or paths.shape[2:] != (arity - 1, 4):
+        raise ValueError("%s: paths must have shape [%d, depth, %d, 4], got %r" % (where, q, arity - 1, paths.shape))
+    _matrix_modes(where, pad_mode, out_idx)
+    idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+    if idx.size != q:
+        raise ValueError("%s: %d indices for %d rows" % (where, idx.size, q))
+    roots = np.zeros((q, 4), dtype=np.uint64)
+    check(_lib.lib().hades252_matrix_verify(_ptr(rows), rows.shape[1], _ptr(idx), _ptr(paths), q, paths.shape[1], arity,
+                                            _tag_arr(capacity_mont), pad_mode, _tag_arr(tag_mont), out_idx, _ptr(roots)), where)
+    return roots
+
+
 GEN_SEED = 0x4861646573323532
 
 

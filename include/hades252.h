@@ -636,6 +636,62 @@ int hades252_perm_inverse_batch(uint64_t *states, size_t n_perms);
 int hades252_perm_inverse_rounds(uint64_t *states, size_t n_perms, int round_hi, int round_lo);
 int hades252_fifth_root_batch(uint64_t *scalars, size_t n_scalars);
 
+/* ---- column-major matrix commitments: row hashes, tree and openings (f12) ---- CONVENTION UNPINNED
+ * What a prover's trace, a batch of interpolated polynomials or a column-hashing sealer holds: a matrix of n_rows x n_cols
+ * scalars stored column by column, each column one contiguous array ("plane") with one entry per row,
+ *   scalar (r, c) = planes[(c * plane_stride + r) * 4 .. +4]          (4 Montgomery limbs, fully reduced, not checked).
+ * Every row is hashed, the digests are put under a Merkle tree, and rows are opened with their paths -- without the caller
+ * transposing anything.  Everything is defined through what the library already computes (the conventions are those of the
+ * sponge f1 and the tree f2: capacity, padding and tag are parameters, still unpinned):
+ *   leaf[r]   the digest hades252_sponge_hash gives for the message (M[r][0], ..., M[r][n_cols - 1]) with the same
+ *             capacity_mont and pad_mode;
+ *   the tree  byte for byte what hades252_merkle_build_pad_dev writes over those leaves: same level order, same padding
+ *             rule, same `pad` table (depth digests, here in HOST memory; NULL = zeros); the root is its last 32 bytes;
+ *   opening   of row r: the row itself, row-major (n_cols scalars), and its path in the layout of
+ *             hades252_merkle_open_pad_dev; an index >= n_rows yields an all-zero row and path, as hades252_merkle_open_dev
+ *             does (nothing outside the matrix or the tree is read).
+ *   hades252_matrix_row_digests   the leaves only: n_rows x 32 bytes
+ *   hades252_matrix_commit        digests, tree and root in one call; digests and tree may each be NULL (not wanted, nothing
+ *                                 is written through them), root may not.  tree: hades252_merkle_tree_bytes(n_rows, arity)
+ *                                 bytes.  The digests never visit the host between the hashing and the tree.
+ *   hades252_matrix_open          openings from what commit returned (digests and tree both needed): a gather in plain host
+ *                                 code that touches no device.  rows_out: n_queries x n_cols scalars; paths_out: n_queries x
+ *                                 depth x (arity - 1) x 32 bytes, depth = hades252_merkle_depth(n_rows, arity).  Duplicate and
+ *                                 unsorted indices are fine.
+ *   hades252_matrix_verify        roots[t] = the root recomputed from opened row t (rows: n_queries x n_cols scalars,
+ *                                 row-major), its index and its path; the caller compares with the committed root.
+ * Host memory in and out, synchronous.  The rows travel in chunks of K rows (a multiple of 256; up to 128 MiB over all
+ * columns and at most 2^18 rows), one 2-D copy per chunk into one of two device buffers, and chunk i + 1 is copied while
+ * chunk i is hashed: device memory is two chunks, n_rows x 32 bytes of digests and the tree, whatever the matrix.  A chunk's
+ * kernel takes one permutation latency per block of four columns however few rows it has, so a matrix of more than about 64
+ * columns (fewer than 2^16 rows per chunk) is bound by that latency, not by the link.  Page-locked planes
+ * (hades252_host_alloc / hades252_host_register) are recommended: from pageable memory the 2-D copies do not overlap the
+ * kernel.
+ * There is no device-pointer form (a block of a row is 128 bytes in for one permutation, against 160 in and 160 out for
+ * hades252_perm_batch, so the copies are expected to hide behind the kernel), no canonical-bytes form, no witness form, and
+ * only one kernel form, one row per lane: a matrix of a few hundred rows pays one permutation latency (about 160 us) per
+ * block of four columns; there is no one-row-per-wave latency form.  hades252_matrix_verify does use the latency forms of
+ * hades252_sponge_hash_dev and hades252_merkle_verify_dev for small batches of queries.
+ * Rules, all decided before the device is touched: n_rows = 0 is a no-op success for hades252_matrix_row_digests and
+ * n_queries = 0 for hades252_matrix_open and hades252_matrix_verify, even with NULL pointers; a NULL pointer that is needed
+ * (planes, capacity_mont, tag_mont, root, indices, the outputs of row_digests / open / verify, digests and tree for open),
+ * a pointer that is not 8-byte aligned, n_cols outside 1 .. HADES252_MATRIX_MAX_COLS, plane_stride < n_rows, pad_mode other
+ * than 0 or 1, arity outside 2 .. 4, out_idx outside 0 .. 4, n_rows < 2 for commit and open (hades252_merkle_depth is -1),
+ * n_rows or n_queries above 2^30, a depth outside 1 .. 64 for verify, or a byte count that overflows size_t is
+ * HADES252_ERR_INVALID_ARG.  No device: HADES252_ERR_NO_DEVICE (there is no CPU fallback; hades252_matrix_open needs none). */
+#define HADES252_MATRIX_MAX_COLS 4096      /* so the smallest chunk (256 rows) is 32 MiB */
+int hades252_matrix_row_digests(const uint64_t *planes, size_t n_rows, size_t n_cols, size_t plane_stride,
+                                const uint64_t capacity_mont[4], int pad_mode, uint64_t *digests);
+int hades252_matrix_commit(const uint64_t *planes, size_t n_rows, size_t n_cols, size_t plane_stride,
+                           const uint64_t capacity_mont[4], int pad_mode, int arity, const uint64_t tag_mont[4], int out_idx,
+                           const uint64_t *pad, uint64_t *digests, uint64_t *tree, uint64_t root[4]);
+int hades252_matrix_open(const uint64_t *planes, size_t n_rows, size_t n_cols, size_t plane_stride, const uint64_t *digests,
+                         const uint64_t *tree, int arity, const uint64_t *pad, const uint64_t *indices, size_t n_queries,
+                         uint64_t *rows_out, uint64_t *paths_out);
+int hades252_matrix_verify(const uint64_t *rows, size_t n_cols, const uint64_t *indices, const uint64_t *paths, size_t n_queries,
+                           int depth, int arity, const uint64_t capacity_mont[4], int pad_mode, const uint64_t tag_mont[4],
+                           int out_idx, uint64_t *roots);
+
 /* ---- synthetic inputs and digests (benchmark / verification plumbing) --------------------- */
 /* Generator B: scalar e (global element index first_elem + k) gets 4 splitmix64 limbs, top limb
  * masked to 62 bits (always < p); see DESIGN.md.  Stateless, so shards generate independently. */

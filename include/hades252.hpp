@@ -248,6 +248,45 @@ inline void perm_inverse_rounds(BlsScalar *states, std::size_t n_perms, int roun
 inline void fifth_root(BlsScalar *scalars, std::size_t n_scalars) {
     check(hades252_fifth_root_batch(reinterpret_cast<std::uint64_t *>(scalars), n_scalars), "fifth_root");
 }
+// Commitments to a matrix held column by column in host memory (include/hades252.h, CONVENTION UNPINNED like the sponge and
+// the tree they are made of): scalar (r, c) = planes[c * plane_stride + r].  The row digests are those of sponge_hash on
+// the transposed matrix, the tree is the one hades252_merkle_build_pad_dev writes (pad: depth digests or nullptr).  Host
+// pointers only.  matrix_commit: digests and tree may be nullptr (not wanted); the root is returned.  matrix_open is plain
+// host code (rows_out: n_queries x n_cols, paths_out: n_queries x depth x (arity - 1)); matrix_verify recomputes one root
+// per opened row for the caller to compare.
+inline void matrix_row_digests(const BlsScalar *planes, std::size_t n_rows, std::size_t n_cols, std::size_t plane_stride,
+                               const BlsScalar &capacity, bool pad_one, BlsScalar *digests) {
+    check(hades252_matrix_row_digests(reinterpret_cast<const std::uint64_t *>(planes), n_rows, n_cols, plane_stride,
+                                      capacity.limbs, pad_one ? 1 : 0, reinterpret_cast<std::uint64_t *>(digests)),
+          "matrix_row_digests");
+}
+inline BlsScalar matrix_commit(const BlsScalar *planes, std::size_t n_rows, std::size_t n_cols, std::size_t plane_stride,
+                               const BlsScalar &capacity, bool pad_one, int arity, const BlsScalar &tag, int out_idx = 1,
+                               const BlsScalar *pad = nullptr, BlsScalar *digests = nullptr, BlsScalar *tree = nullptr) {
+    BlsScalar root{};
+    check(hades252_matrix_commit(reinterpret_cast<const std::uint64_t *>(planes), n_rows, n_cols, plane_stride, capacity.limbs,
+                                 pad_one ? 1 : 0, arity, tag.limbs, out_idx, reinterpret_cast<const std::uint64_t *>(pad),
+                                 reinterpret_cast<std::uint64_t *>(digests), reinterpret_cast<std::uint64_t *>(tree), root.limbs),
+          "matrix_commit");
+    return root;
+}
+inline void matrix_open(const BlsScalar *planes, std::size_t n_rows, std::size_t n_cols, std::size_t plane_stride,
+                        const BlsScalar *digests, const BlsScalar *tree, int arity, const BlsScalar *pad,
+                        const std::uint64_t *indices, std::size_t n_queries, BlsScalar *rows_out, BlsScalar *paths_out) {
+    check(hades252_matrix_open(reinterpret_cast<const std::uint64_t *>(planes), n_rows, n_cols, plane_stride,
+                               reinterpret_cast<const std::uint64_t *>(digests), reinterpret_cast<const std::uint64_t *>(tree),
+                               arity, reinterpret_cast<const std::uint64_t *>(pad), indices, n_queries,
+                               reinterpret_cast<std::uint64_t *>(rows_out), reinterpret_cast<std::uint64_t *>(paths_out)),
+          "matrix_open");
+}
+inline void matrix_verify(const BlsScalar *rows, std::size_t n_cols, const std::uint64_t *indices, const BlsScalar *paths,
+                          std::size_t n_queries, int depth, int arity, const BlsScalar &capacity, bool pad_one,
+                          const BlsScalar &tag, int out_idx, BlsScalar *roots) {
+    check(hades252_matrix_verify(reinterpret_cast<const std::uint64_t *>(rows), n_cols, indices,
+                                 reinterpret_cast<const std::uint64_t *>(paths), n_queries, depth, arity, capacity.limbs,
+                                 pad_one ? 1 : 0, tag.limbs, out_idx, reinterpret_cast<std::uint64_t *>(roots)),
+          "matrix_verify");
+}
 // DEVICE memory, enqueued on `stream`: the whole pattern in one launch, or call by call on the 160-byte states of
 // hades252_sponge_init_dev with a caller-owned cursor (0 = fresh) that moves with every call.
 inline void safe_hash_dev(const void *d_in, std::size_t n_msgs, const std::uint32_t *calls, std::size_t n_calls,
