@@ -166,6 +166,13 @@ SIGNATURES = {
                                      c_size_t, c_void_p, c_void_p]),
     "hades252_matrix_verify": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int, c_int, POINTER(c_uint64), c_int,
                                        POINTER(c_uint64), c_int, c_void_p]),
+    "hades252_matstream_open": (c_int, [POINTER(c_void_p), c_size_t, POINTER(c_uint64)]),
+    "hades252_matstream_absorb": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t]),
+    "hades252_matstream_cols": (c_int, [c_void_p, POINTER(c_uint64)]),
+    "hades252_matstream_digests": (c_int, [c_void_p, c_int, c_void_p]),
+    "hades252_matstream_commit": (c_int, [c_void_p, c_int, c_int, POINTER(c_uint64), c_int, c_void_p, c_void_p, c_void_p,
+                                          c_void_p]),
+    "hades252_matstream_close": (c_int, [c_void_p]),
     "hades252_gen_b_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_uint64, c_void_p]),
     "hades252_gen_a_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_void_p]),
     "hades252_digest_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_void_p, c_void_p]),

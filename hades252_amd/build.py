@@ -49,7 +49,12 @@ INVERSE_DEPS = ["kernels_inverse.hpp", "hades_inverse_constants.inc", "host_inve
 # every other source (DEPS), outside device_source_hash and perm_fast_hash.  The host simulation runs the kernel from a
 # driver of its own (tests/hostsim_matrix).
 MATRIX_DEPS = ["kernels_matrix.hpp", "host_matrix.hpp"]
-DEPS = HOST_DEPS + LAUNCH_POLICY_DEPS + DEVICE_DEPS + UNRECORDED_KERNEL_DEPS + GRIND_DEPS + INVERSE_DEPS + MATRIX_DEPS + [os.path.join("..", "..", "include", "hades252.h")]
+# streaming matrix commitments (the row sponges stay resident on the device, the matrix arrives a group of columns at a
+# time): their kernels and host calls, host pointers only.  As MATRIX_DEPS: rebuilt like every other source (DEPS), outside
+# device_source_hash and perm_fast_hash.  The host simulation runs the kernels from a driver of its own
+# (tests/hostsim_matrix_stream).
+MATRIX_STREAM_DEPS = ["kernels_matrix_stream.hpp", "host_matrix_stream.hpp"]
+DEPS = HOST_DEPS + LAUNCH_POLICY_DEPS + DEVICE_DEPS + UNRECORDED_KERNEL_DEPS + GRIND_DEPS + INVERSE_DEPS + MATRIX_DEPS + MATRIX_STREAM_DEPS + [os.path.join("..", "..", "include", "hades252.h")]
 # what the dominant kernel (k_perm_fast) is made of: profiles recorded for it stay valid while these are unchanged
 PERM_FAST_DEPS = ["fr32.hpp", "staging.hpp", "hades_fast.hpp", "k_perm_fast.hpp"]
 # ... plus these tables of hades_constants.inc (other kernels' tables may change without touching k_perm_fast)

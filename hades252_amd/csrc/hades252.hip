@@ -37,6 +37,7 @@ using namespace hades;
 #include "hades_inverse_constants.inc"
 #include "kernels_inverse.hpp"
 #include "kernels_matrix.hpp"
+#include "kernels_matrix_stream.hpp"
 #include "kernels_witness.hpp"
 #include "kernels_aux.hpp"
 
@@ -61,4 +62,5 @@ using namespace hades;
 #include "host_grind.hpp"
 #include "host_inverse.hpp"
 #include "host_matrix.hpp"
+#include "host_matrix_stream.hpp"
 #include "host_cipher.hpp"

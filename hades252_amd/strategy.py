@@ -1357,6 +1357,98 @@ def matrix_verify_host(rows: np.ndarray, indices, paths: np.ndarray, arity: int,
     return roots
 
 
+class MatrixStream:
+    """``hades252_matstream_*``: a commitment to a column-major matrix of ``n_rows`` rows that arrives a group of columns at
+    a time; the row sponges stay on the device between the calls.  After absorbs of g_1, ..., g_k columns, ``digests`` and
+    ``commit`` give what matrix_row_digests_host / matrix_commit_host give for the concatenated matrix, and leave the stream
+    as it is: it can go on absorbing, so every prefix can be committed to.  HOST numpy arrays in and out; a context manager::
+
+        with MatrixStream(n_rows, capacity_mont) as ms:
+            for group in groups:              # uint64 [g, plane_stride, 4], plane_stride >= n_rows
+                ms.absorb(group)
+            digests, tree, root = ms.commit(arity, tag_mont)
+    """
+
+    def __init__(self, n_rows: int, capacity_mont: int):
+        self._h = None
+        if not isinstance(n_rows, int) or isinstance(n_rows, bool) or not 1 <= n_rows <= 1 << 30:
+            raise ValueError("MatrixStream: n_rows must be 1 .. 2^30, got %r" % (n_rows,))
+        h = ctypes.c_void_p()
+        check(_lib.lib().hades252_matstream_open(ctypes.byref(h), n_rows, _tag_arr(capacity_mont)), "MatrixStream")
+        self._h, self.n_rows = h, n_rows
+
+    def _handle(self, where: str):
+        if self._h is None:
+            raise ValueError("%s: the stream is closed" % where)
+        return self._h
+
+    def absorb(self, planes: np.ndarray, n_rows: int | None = None) -> "MatrixStream":
+        """The next columns of every row: ``planes`` uint64 [g, plane_stride, 4] (Montgomery limbs), rows 0 .. n_rows - 1 of
+        every plane.  ``n_rows``, when given, must be the stream's.  Synchronous; g = 0 is a no-op."""
+        where = "MatrixStream.absorb"
+        h = self._handle(where)
+        planes = _host_u64(planes, where)
+        if planes.ndim != 3 or planes.shape[2] != 4:
+            raise ValueError("%s: planes must have shape [n_cols, plane_stride, 4], got %r" % (where, planes.shape))
+        if n_rows is not None and n_rows != self.n_rows:
+            raise ValueError("%s: the stream has %d rows, got n_rows = %r" % (where, self.n_rows, n_rows))
+        if planes.shape[1] < self.n_rows:
+            raise ValueError("%s: planes of %d rows for a stream of %d" % (where, planes.shape[1], self.n_rows))
+        check(_lib.lib().hades252_matstream_absorb(h, _ptr(planes), planes.shape[0], planes.shape[1]), where)
+        return self
+
+    @property
+    def cols(self) -> int:
+        """Columns absorbed so far."""
+        h, n = self._handle("MatrixStream.cols"), ctypes.c_uint64()
+        check(_lib.lib().hades252_matstream_cols(h, ctypes.byref(n)), "MatrixStream.cols")
+        return int(n.value)
+
+    def digests(self, pad_mode: int = 1) -> np.ndarray:
+        """The row digests [n_rows, 4] of the columns absorbed so far; the stream is left as it is."""
+        where = "MatrixStream.digests"
+        h = self._handle(where)
+        _matrix_modes(where, pad_mode)
+        out = np.zeros((self.n_rows, 4), dtype=np.uint64)
+        check(_lib.lib().hades252_matstream_digests(h, pad_mode, _ptr(out)), where)
+        return out
+
+    def commit(self, arity: int, tag_mont: int, pad_mode: int = 1, out_idx: int = 1, pad: np.ndarray | None = None,
+               want_digests: bool = True, want_tree: bool = True):
+        """(digests [n_rows, 4] or None, tree [nodes, 4] or None, root [4]) of the columns absorbed so far, as
+        matrix_commit_host gives them (``pad``: host table [depth, 4] or None); the stream is left as it is."""
+        where = "MatrixStream.commit"
+        h = self._handle(where)
+        depth, nodes = _matrix_tree_shape(where, self.n_rows, arity)
+        _matrix_modes(where, pad_mode, out_idx)
+        pptr = _matrix_pad(where, pad, depth)
+        digests = np.zeros((self.n_rows, 4), dtype=np.uint64) if want_digests else None
+        tree = np.zeros((nodes, 4), dtype=np.uint64) if want_tree else None
+        root = np.zeros(4, dtype=np.uint64)
+        check(_lib.lib().hades252_matstream_commit(h, pad_mode, arity, _tag_arr(tag_mont), out_idx, pptr,
+                                                   None if digests is None else _ptr(digests),
+                                                   None if tree is None else _ptr(tree), _ptr(root)), where)
+        return digests, tree, root
+
+    def close(self) -> None:
+        """Frees what the stream holds on the device; closing twice is fine."""
+        h, self._h = self._h, None
+        if h is not None:
+            _lib.lib().hades252_matstream_close(h)
+
+    def __enter__(self) -> "MatrixStream":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 GEN_SEED = 0x4861646573323532
 
 

@@ -664,7 +664,8 @@ int hades252_fifth_root_batch(uint64_t *scalars, size_t n_scalars);
  * columns and at most 2^18 rows), one 2-D copy per chunk into one of two device buffers, and chunk i + 1 is copied while
  * chunk i is hashed: device memory is two chunks, n_rows x 32 bytes of digests and the tree, whatever the matrix.  A chunk's
  * kernel takes one permutation latency per block of four columns however few rows it has, so a matrix of more than about 64
- * columns (fewer than 2^16 rows per chunk) is bound by that latency, not by the link.  Page-locked planes
+ * columns (fewer than 2^16 rows per chunk) is bound by that latency, not by the link; the streaming form (f13, below) takes
+ * such a matrix in column groups over all rows and is not.  Page-locked planes
  * (hades252_host_alloc / hades252_host_register) are recommended: from pageable memory the 2-D copies do not overlap the
  * kernel.
  * There is no device-pointer form (a block of a row is 128 bytes in for one permutation, against 160 in and 160 out for
@@ -691,6 +692,60 @@ int hades252_matrix_open(const uint64_t *planes, size_t n_rows, size_t n_cols, s
 int hades252_matrix_verify(const uint64_t *rows, size_t n_cols, const uint64_t *indices, const uint64_t *paths, size_t n_queries,
                            int depth, int arity, const uint64_t capacity_mont[4], int pad_mode, const uint64_t tag_mont[4],
                            int out_idx, uint64_t *roots);
+
+/* ---- streaming matrix commitments: column groups, resident row states (f13) ---- CONVENTION UNPINNED
+ * The commitment of f12 for a matrix that is produced a group of columns at a time and may never be in host memory at once
+ * (a trace and its low-degree extension, batches of interpolated polynomials): a stream is opened for n_rows rows, fed any
+ * number of columns per call and finished at any point.  The row sponges stay on the device between the calls.
+ * Everything is defined through f12.  After absorbs of g_1, ..., g_k columns let M be the n_rows x (g_1 + ... + g_k) matrix
+ * of those columns in order:
+ *   hades252_matstream_open      a stream for n_rows rows with this capacity word; *out is the handle (NULL on any failure).
+ *                                It owns 160 bytes of device memory per row and, from the first digests / commit on, n_rows x
+ *                                32 bytes of digests and the tree.  hades252_trim does not free what an open stream holds.
+ *   hades252_matstream_absorb    the next n_cols columns, every row: scalar (r, j) of the group = planes[(j * plane_stride + r)
+ *                                * 4 .. +4], layout and rules of f12, each call with its own planes and plane_stride.
+ *                                Synchronous: the caller may reuse planes when it returns.
+ *   hades252_matstream_cols      the number of columns absorbed so far
+ *   hades252_matstream_digests   writes what hades252_matrix_row_digests(M, ..., pad_mode) writes
+ *   hades252_matstream_commit    writes what hades252_matrix_commit(M, ...) writes: same digests, tree and root, same `pad`
+ *                                table (depth digests in HOST memory; NULL = zeros); digests and tree may each be NULL, root
+ *                                may not.  The digests never visit the host between the hashing and the tree.
+ *   hades252_matstream_close     frees the stream; close(NULL) is a no-op success.
+ * The padding is chosen at the end, not at open: it happens only there.  digests and commit are NON-DESTRUCTIVE -- they pad
+ * and finish a copy of the state -- so the stream can go on absorbing afterwards and a caller may commit to every prefix.
+ * State per row after c columns: the five-word sponge state with floor(c / 4) blocks added into words 1..4 and permuted and
+ * the c % 4 columns of the open block added and not permuted.  Finish: under pad_mode 1 Montgomery one is added into word
+ * 1 + c % 4; a permutation if c % 4 != 0 or pad_mode == 1; the digest is word 1 (hades252_sponge_blocks(c, pad_mode)
+ * permutations in all).
+ * A group travels in tiles of K rows x G columns (K = all rows up to 2^18, G = 128 MiB / (32 K) columns, a multiple of
+ * four), one 2-D copy per tile into one of two device buffers, tile t + 1 copied while tile t is absorbed: a wide matrix
+ * runs as full-device launches of a few blocks each, where hades252_matrix_commit (whose chunk holds all columns, hence
+ * few rows) pays one permutation latency per block of four columns and chunk: 2^16 rows x 1 024 columns take 52 ms against
+ * 738 ms (one MI355X, profiles/f13_matrix_stream/), and what is left is the chain of dependent permutations of a row.  A
+ * call that is a single tile cannot overlap its copy with its kernel: feed several tiles per call where possible.  The
+ * stream pays 320 bytes of device traffic per row and launch for its state, so a narrow matrix that is in memory anyway
+ * gains nothing.  Page-locked planes are recommended, as for f12.
+ * Host pointers only, like f10 to f12: no device-pointer form, no canonical-bytes form, no witness form, no latency form,
+ * no openings (hades252_matrix_open gathers rows from whatever planes the caller still holds, a group at a time).
+ * A stream is used by one thread at a time and with the device current that was current at open (with another one the
+ * call is HADES252_ERR_INVALID_ARG); different streams, and streams alongside any other call of the library, are independent.
+ * Rules, all decided before the device is touched.  open: out or capacity_mont NULL, n_rows 0 or above 2^30 is
+ * HADES252_ERR_INVALID_ARG; no device is HADES252_ERR_NO_DEVICE.  Every other call with a NULL stream is
+ * HADES252_ERR_INVALID_ARG, except close.  absorb: n_cols = 0 is a no-op success, even with NULL planes; NULL planes or
+ * planes that are not 8-byte aligned, plane_stride < n_rows, a byte count that overflows size_t or a column total that
+ * overflows uint64_t is HADES252_ERR_INVALID_ARG; there is no cap on the number of columns, per call or in total.  digests
+ * and commit: no column absorbed so far, pad_mode other than 0 or 1, a NULL or misaligned output that is needed is
+ * HADES252_ERR_INVALID_ARG; commit applies the rules of hades252_matrix_commit besides (n_rows >= 2, arity 2 .. 4, out_idx
+ * 0 .. 4, tag_mont and root not NULL, 8-byte alignment).  An HADES252_ERR_INVALID_ARG leaves the stream exactly as it was.
+ * A HIP failure inside a call returns HADES252_ERR_HIP and poisons the stream: every later absorb, digests or commit
+ * returns HADES252_ERR_HIP without touching the device, cols still answers with the last good total, close always works. */
+int hades252_matstream_open(void **out, size_t n_rows, const uint64_t capacity_mont[4]);
+int hades252_matstream_absorb(void *ms, const uint64_t *planes, size_t n_cols, size_t plane_stride);
+int hades252_matstream_cols(const void *ms, uint64_t *n_cols_so_far);
+int hades252_matstream_digests(void *ms, int pad_mode, uint64_t *digests);
+int hades252_matstream_commit(void *ms, int pad_mode, int arity, const uint64_t tag_mont[4], int out_idx, const uint64_t *pad,
+                              uint64_t *digests, uint64_t *tree, uint64_t root[4]);
+int hades252_matstream_close(void *ms);
 
 /* ---- synthetic inputs and digests (benchmark / verification plumbing) --------------------- */
 /* Generator B: scalar e (global element index first_elem + k) gets 4 splitmix64 limbs, top limb

@@ -287,6 +287,61 @@ inline void matrix_verify(const BlsScalar *rows, std::size_t n_cols, const std::
                                  pad_one ? 1 : 0, tag.limbs, out_idx, reinterpret_cast<std::uint64_t *>(roots)),
           "matrix_verify");
 }
+// The same commitment for a matrix that arrives a group of columns at a time (include/hades252.h, hades252_matstream_*): the
+// row sponges stay on the device between the calls.  After absorbs of g_1, ..., g_k columns, digests and commit give what
+// matrix_row_digests and matrix_commit give for the concatenated matrix and leave the stream as it is, so it can go on
+// absorbing.  Host pointers only.  Movable, closes on destruction.
+class MatrixStream {
+    void *h_ = nullptr;
+    std::size_t n_rows_ = 0;
+
+public:
+    MatrixStream(std::size_t n_rows, const BlsScalar &capacity) : n_rows_(n_rows) {
+        check(hades252_matstream_open(&h_, n_rows, capacity.limbs), "MatrixStream");
+    }
+    MatrixStream(const MatrixStream &) = delete;
+    MatrixStream &operator=(const MatrixStream &) = delete;
+    MatrixStream(MatrixStream &&o) noexcept : h_(o.h_), n_rows_(o.n_rows_) { o.h_ = nullptr; o.n_rows_ = 0; }
+    MatrixStream &operator=(MatrixStream &&o) noexcept {
+        if (this != &o) {
+            close();
+            h_ = o.h_;
+            n_rows_ = o.n_rows_;
+            o.h_ = nullptr;
+            o.n_rows_ = 0;
+        }
+        return *this;
+    }
+    ~MatrixStream() { close(); }
+    void close() noexcept {
+        if (h_) (void)hades252_matstream_close(h_);
+        h_ = nullptr;
+    }
+    std::size_t n_rows() const { return n_rows_; }
+    // the next n_cols columns of every row: scalar (r, j) = planes[j * plane_stride + r]
+    void absorb(const BlsScalar *planes, std::size_t n_cols, std::size_t plane_stride) {
+        check(hades252_matstream_absorb(h_, reinterpret_cast<const std::uint64_t *>(planes), n_cols, plane_stride),
+              "MatrixStream::absorb");
+    }
+    std::uint64_t cols() const {
+        std::uint64_t n = 0;
+        check(hades252_matstream_cols(h_, &n), "MatrixStream::cols");
+        return n;
+    }
+    void digests(bool pad_one, BlsScalar *out) {
+        check(hades252_matstream_digests(h_, pad_one ? 1 : 0, reinterpret_cast<std::uint64_t *>(out)), "MatrixStream::digests");
+    }
+    // digests and tree may be nullptr (not wanted); the root is returned
+    BlsScalar commit(bool pad_one, int arity, const BlsScalar &tag, int out_idx = 1, const BlsScalar *pad = nullptr,
+                     BlsScalar *digests = nullptr, BlsScalar *tree = nullptr) {
+        BlsScalar root{};
+        check(hades252_matstream_commit(h_, pad_one ? 1 : 0, arity, tag.limbs, out_idx, reinterpret_cast<const std::uint64_t *>(pad),
+                                        reinterpret_cast<std::uint64_t *>(digests), reinterpret_cast<std::uint64_t *>(tree),
+                                        root.limbs),
+              "MatrixStream::commit");
+        return root;
+    }
+};
 // DEVICE memory, enqueued on `stream`: the whole pattern in one launch, or call by call on the 160-byte states of
 // hades252_sponge_init_dev with a caller-owned cursor (0 = fresh) that moves with every call.
 inline void safe_hash_dev(const void *d_in, std::size_t n_msgs, const std::uint32_t *calls, std::size_t n_calls,
