@@ -120,10 +120,15 @@ class StagedSource {
 struct HostCall {                 // releases what a one-shot host call holds, whichever way it ends
     HostPipe pipe;
     StagedSource *src = nullptr;  // upload through staging threads (input in ordinary memory)
-    bool have_pipe = false;
+    // takes a pipe from the pool (acquire_pipe); finish() gives it back
+    int acquire(size_t slot_bytes, bool want_stage = false) {
+        const int rc = acquire_pipe(slot_bytes, pipe, want_stage);
+        if (rc == HADES252_OK) have_pipe = true;
+        return rc;
+    }
     // decides how the input travels: through staging threads when it is big, in ordinary memory and HADES252_HOST_PIN
     // allows; else straight from the caller's memory (DMA if page-locked, the runtime's pageable copy otherwise).
-    // *chunk_bytes is clamped to a staging slot in the first case.  Call after acquire_pipe.
+    // *chunk_bytes is clamped to a staging slot in the first case.  Call after acquire.
     static bool will_stage(const void *h, size_t bytes) {
         return host_pin_enabled() && bytes >= ((size_t)8 << 20) && !host_range_pinned(h, bytes);
     }
@@ -159,6 +164,9 @@ struct HostCall {                 // releases what a one-shot host call holds, w
         tl_last_hip_error = src ? src->hip_error() : (int)hipErrorUnknown;
         return finish(HADES252_ERR_HIP);
     }
+
+  private:
+    bool have_pipe = false;
 };
 
 // (also used by host_cipher.hpp, included right after this file, which #undefs it)
@@ -187,9 +195,8 @@ static int merkle_root_host(const uint64_t *leaves, size_t n_leaves, int arity, 
     const size_t scratch = hades252_merkle_scratch_bytes(n1, arity);  // 0 unless the tree over level 1 has >= 2 levels
     const size_t head = (size_t)depth * 32 + 32;                      // padding table, root
     HostCall call;
-    rc = acquire_pipe(chunk * 32, call.pipe, HostCall::will_stage(leaves, n_leaves * 32));
+    rc = call.acquire(chunk * 32, HostCall::will_stage(leaves, n_leaves * 32));
     if (rc != HADES252_OK) return rc;
-    call.have_pipe = true;
     HostPipe &pp = call.pipe;
     {
         size_t cbytes = chunk * 32;
@@ -252,10 +259,9 @@ int hades252_sponge_hash(const uint64_t *msgs, size_t n_msgs, size_t msg_len, co
     if (chunk > n_msgs) chunk = n_msgs;
     if (chunk > kMaxLaunchRecords) chunk = kMaxLaunchRecords;
     HostCall call;
-    rc = acquire_pipe(chunk * msg_bytes > 16 ? chunk * msg_bytes : 16, call.pipe,
+    rc = call.acquire(chunk * msg_bytes > 16 ? chunk * msg_bytes : 16,
                       msg_bytes && msg_bytes <= StagedSource::slot_bytes() && HostCall::will_stage(msgs, n_msgs * msg_bytes));
     if (rc != HADES252_OK) return rc;
-    call.have_pipe = true;
     HostPipe &pp = call.pipe;
     if (msg_bytes && msg_bytes <= StagedSource::slot_bytes()) {
         size_t cbytes = chunk * msg_bytes;
@@ -360,9 +366,8 @@ int hades252_sponge_hash_var(const uint64_t *scalars, size_t n_scalars, const ui
     const size_t pool_b = up16(n_scalars * 32 + 16), idx_b = up16(n_msgs * 8), dig_b = n_msgs * 32;
     const size_t scr_b = up16(hades252_sponge_sort_scratch_bytes(n_msgs));
     HostCall call;
-    rc = acquire_pipe(16, call.pipe, n_scalars && HostCall::will_stage(scalars, n_scalars * 32));
+    rc = call.acquire(16, n_scalars && HostCall::will_stage(scalars, n_scalars * 32));
     if (rc != HADES252_OK) return rc;
-    call.have_pipe = true;
     HostPipe &pp = call.pipe;
     rc = pipe_ensure_aux(pp, pool_b + 2 * idx_b + dig_b + scr_b + 16);
     if (rc != HADES252_OK) return call.finish(rc);

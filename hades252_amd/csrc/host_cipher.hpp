@@ -26,9 +26,8 @@ static int cipher_host(bool decrypt, const uint64_t *in, const uint64_t *keys, c
     const size_t in_b = up16(chunk * in_words * 32), key_b = chunk * 64, nonce_b = chunk * 32,
                  out_b = up16(chunk * out_words * 32), ok_b = up16(chunk);
     HostCall call;
-    rc = acquire_pipe(16, call.pipe);
+    rc = call.acquire(16);
     if (rc != HADES252_OK) return rc;
-    call.have_pipe = true;
     HostPipe &pp = call.pipe;
     rc = pipe_ensure_aux(pp, in_b + key_b + nonce_b + out_b + ok_b + 16);
     if (rc != HADES252_OK) return call.finish(rc);

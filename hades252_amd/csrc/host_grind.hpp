@@ -52,9 +52,8 @@ int hades252_grind(const uint64_t *seeds, size_t n_jobs, int word, int out_idx, 
     const size_t seeds_b = n_jobs * 160, slots_b = n_jobs * 8;
     std::vector<uint64_t> h_slots(n_jobs, UINT64_MAX);                     // all-ones: no hit yet
     HostCall call;
-    rc = acquire_pipe(16, call.pipe);
+    rc = call.acquire(16);
     if (rc != HADES252_OK) return rc;
-    call.have_pipe = true;
     HostPipe &pp = call.pipe;
     rc = pipe_ensure_aux(pp, seeds_b + slots_b + 16);
     if (rc != HADES252_OK) return call.finish(rc);

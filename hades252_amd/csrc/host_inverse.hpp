@@ -24,9 +24,8 @@ static int inverse_host(bool scalars, uint64_t *data, size_t n, int round_hi, in
     if (chunk > kMaxLaunchRecords) chunk = kMaxLaunchRecords;
     const size_t buf_b = (chunk * rec_bytes + 255) & ~(size_t)255;
     HostCall call;
-    rc = acquire_pipe(16, call.pipe);
+    rc = call.acquire(16);
     if (rc != HADES252_OK) return rc;
-    call.have_pipe = true;
     HostPipe &pp = call.pipe;
     rc = pipe_ensure_aux(pp, 2 * buf_b);
     if (rc != HADES252_OK) return call.finish(rc);

@@ -19,19 +19,20 @@ static constexpr size_t kMatrixTargetBytes = (size_t)128 << 20;
 // that a larger chunk hashes no faster and only lengthens the first copy, which nothing overlaps (4 columns, 2^20 rows:
 // see the same file for one chunk of 2^20 rows against four of 2^18).
 static constexpr size_t kMatrixFullRows = (size_t)1 << 18;
-// Rows per chunk: a multiple of 256 (whole blocks), at least 256 -- with HADES252_MATRIX_MAX_COLS columns that is 32 MiB.
+// Rows per chunk of a matrix of n_rows rows: a multiple of 256 (whole blocks), at least 256 -- with
+// HADES252_MATRIX_MAX_COLS columns that is 32 MiB -- and no more than the matrix has.
 // Test hook: HADES252_TEST_MATRIX_CHUNK_ROWS (read once, at the first call) sets it, rounded down to a multiple of 256, so
 // that a matrix of a thousand rows runs through several chunks (tests/test_gpu_f12_matrix.py) and the chunk size can be
 // A/B-ed (tools/time_matrix.py); values below 256 are ignored.
-static size_t matrix_chunk_rows(size_t n_cols) {
+static size_t matrix_tile_rows(size_t n_cols, size_t n_rows) {
     static const size_t forced = []() -> size_t {
         const char *e = getenv("HADES252_TEST_MATRIX_CHUNK_ROWS");
         const size_t t = e ? (size_t)strtoull(e, nullptr, 0) : 0;
         return t >= 256 ? t / 256 * 256 : 0;
     }();
-    if (forced) return forced;
-    const size_t k = kMatrixTargetBytes / (32 * n_cols) / 256 * 256;
-    return k < 256 ? 256 : (k > kMatrixFullRows ? kMatrixFullRows : k);
+    const size_t k = kMatrixTargetBytes / (32 * n_cols) / 256 * 256, all = (n_rows + 255) / 256 * 256;
+    const size_t K = forced ? forced : k < 256 ? 256 : (k > kMatrixFullRows ? kMatrixFullRows : k);
+    return K > all ? all : K;
 }
 
 static inline bool host_misaligned(const void *p) { return ((uintptr_t)p & 7u) != 0; }
@@ -43,30 +44,64 @@ static bool matrix_shape_ok(const uint64_t *planes, size_t n_rows, size_t n_cols
            plane_stride >= n_rows && n_rows <= kMaxLaunchRecords && plane_stride <= SIZE_MAX / 32 / n_cols;
 }
 
-// Rows -> digests, chunk by chunk through a pooled pipe: chunk c + 1 travels (one 2-D copy: n_cols pieces of K * 32 bytes,
-// source pitch plane_stride * 32, into a buffer whose plane stride is K) on the copy stream while chunk c is hashed on the
-// kernel stream; the digests accumulate in d_dig (n_rows * 32 bytes, device).  The host runs at most two chunks ahead.
-// From memory that is not page-locked the runtime stages the 2-D copies itself and they do not overlap the kernel.
+// The two-buffer pipeline around the launch of tile t, whose buffer (t % 2) is d: the tile travels (one 2-D copy: `cols`
+// pieces of m * 32 bytes, source pitch stride * 32, into a buffer whose plane stride is K) on the copy stream while tile
+// t - 1 runs on the kernel stream; the host runs at most two tiles ahead.  matrix_tile_in comes before the launch,
+// matrix_tile_launched after it; a failure of either has finished the call and the caller returns the code.  From memory
+// that is not page-locked the runtime stages the 2-D copies itself and they do not overlap the kernel.
+static int matrix_tile_in(HostCall &call, size_t t, uint8_t *d, size_t K, const uint64_t *from, size_t stride, size_t m, size_t cols) {
+    HostPipe &pp = call.pipe;
+    const int k = (int)(t % 2);
+    if (t >= 2) TRY_CALL(call, F(F_SYNC, hipEventSynchronize(pp.k_done[k])));         // tile t - 2 is done: buffer k is free
+    TRY_CALL(call, F(F_MEMCPY, hipMemcpy2DAsync(d, K * 32, from, stride * 32, m * 32, cols, hipMemcpyHostToDevice, pp.s_in)));
+    TRY_CALL(call, hipEventRecord(pp.in_done[k], pp.s_in));
+    TRY_CALL(call, hipStreamWaitEvent(pp.s_k, pp.in_done[k], 0));
+    return HADES252_OK;
+}
+static int matrix_tile_launched(HostCall &call, size_t t) {
+    TRY_CALL(call, hipGetLastError());
+    TRY_CALL(call, hipEventRecord(call.pipe.k_done[t % 2], call.pipe.s_k));
+    return HADES252_OK;
+}
+
+// Rows -> digests, a tile of K rows (all columns) at a time; the digests accumulate in d_dig (n_rows * 32 bytes, device).
 static int matrix_hash_rows(HostCall &call, uint8_t *d_buf, size_t K, const uint64_t *planes, size_t n_rows, size_t n_cols,
                             size_t plane_stride, const uint64_t capacity_mont[4], int pad_mode, uint8_t *d_dig) {
     HostPipe &pp = call.pipe;
-    const uint8_t *h = (const uint8_t *)planes;
     const size_t buf_b = up256(K * n_cols * 32), n_chunks = (n_rows + K - 1) / K;
     const Fr cap = fr_from_u64(capacity_mont);
     for (size_t c = 0; c < n_chunks; c++) {
-        const int k = (int)(c % 2);
         const size_t off = c * K, m = n_rows - off < K ? n_rows - off : K;
-        uint8_t *d = d_buf + (size_t)k * buf_b;
-        if (c >= 2) TRY_CALL(call, F(F_SYNC, hipEventSynchronize(pp.k_done[k])));         // chunk c - 2 is hashed: buffer k is free
-        TRY_CALL(call, F(F_MEMCPY, hipMemcpy2DAsync(d, K * 32, h + off * 32, plane_stride * 32, m * 32, n_cols,
-                                                    hipMemcpyHostToDevice, pp.s_in)));
-        TRY_CALL(call, hipEventRecord(pp.in_done[k], pp.s_in));
-        TRY_CALL(call, hipStreamWaitEvent(pp.s_k, pp.in_done[k], 0));
+        uint8_t *d = d_buf + c % 2 * buf_b;
+        int rc = matrix_tile_in(call, c, d, K, planes + off * 4, plane_stride, m, n_cols);
+        if (rc != HADES252_OK) return rc;
         hipLaunchKernelGGL(k_sponge_planes, dim3(blocks_for(m)), dim3(kBlock), 0, pp.s_k, d, m, n_cols, K, d_dig + off * 32, cap, pad_mode);
-        TRY_CALL(call, hipGetLastError());
-        TRY_CALL(call, hipEventRecord(pp.k_done[k], pp.s_k));
+        rc = matrix_tile_launched(call, c);
+        if (rc != HADES252_OK) return rc;
     }
     return HADES252_OK;
+}
+
+// The end of a commitment, one-shot or streamed, and of its call: the tree over the n_rows digests at d_dig into d_tree
+// (d_pad: the uploaded padding table or NULL; the digests never leave the device in between), then what the caller asked
+// for -- digests (may be NULL), tree (may be NULL) and root (NULL: no tree at all).
+static int matrix_finish(HostCall &call, const uint8_t *d_dig, size_t n_rows, int arity, const uint64_t tag_mont[4], int out_idx,
+                         const uint8_t *d_pad, uint8_t *d_tree, uint64_t *digests, uint64_t *tree, uint64_t *root) {
+    HostPipe &pp = call.pipe;
+    uint64_t got[4];                                                   // the caller's root is written on success only
+    if (root != nullptr) {
+        const size_t tree_bytes = hades252_merkle_tree_bytes(n_rows, arity);
+        const int rc = hades252_merkle_build_pad_dev(d_dig, n_rows, arity, tag_mont, out_idx, d_pad, d_tree, pp.s_k);
+        if (rc != HADES252_OK) return call.finish(rc);
+        if (tree != nullptr)
+            TRY_CALL(call, F(F_MEMCPY, hipMemcpyAsync(tree, d_tree, tree_bytes, hipMemcpyDeviceToHost, pp.s_k)));
+        TRY_CALL(call, F(F_MEMCPY, hipMemcpyAsync(got, d_tree + tree_bytes - 32, 32, hipMemcpyDeviceToHost, pp.s_k)));
+    }
+    if (digests != nullptr)
+        TRY_CALL(call, F(F_MEMCPY, hipMemcpyAsync(digests, d_dig, n_rows * 32, hipMemcpyDeviceToHost, pp.s_k)));
+    TRY_CALL(call, F(F_SYNC, hipStreamSynchronize(pp.s_k)));
+    if (root != nullptr) memcpy(root, got, 32);
+    return call.finish(HADES252_OK);
 }
 
 // digests (may be NULL), tree (may be NULL) and root (NULL: no tree at all -- hades252_matrix_row_digests)
@@ -77,15 +112,12 @@ static int matrix_commit_host(const uint64_t *planes, size_t n_rows, size_t n_co
     const int depth = with_tree ? hades252_merkle_depth(n_rows, arity) : 0;
     int rc = check_device();
     if (rc != HADES252_OK) return rc;
-    size_t K = matrix_chunk_rows(n_cols);
-    if (K > (n_rows + 255) / 256 * 256) K = (n_rows + 255) / 256 * 256;
+    const size_t K = matrix_tile_rows(n_cols, n_rows);
     const size_t buf_b = up256(K * n_cols * 32), dig_b = up256(n_rows * 32);
-    const size_t tree_bytes = with_tree ? hades252_merkle_tree_bytes(n_rows, arity) : 0;
-    const size_t tree_b = up256(tree_bytes), pad_b = up256((size_t)depth * 32);
+    const size_t tree_b = up256(with_tree ? hades252_merkle_tree_bytes(n_rows, arity) : 0), pad_b = up256((size_t)depth * 32);
     HostCall call;
-    rc = acquire_pipe(16, call.pipe);
+    rc = call.acquire(16);
     if (rc != HADES252_OK) return rc;
-    call.have_pipe = true;
     HostPipe &pp = call.pipe;
     rc = pipe_ensure_aux(pp, 2 * buf_b + dig_b + tree_b + pad_b);
     if (rc != HADES252_OK) return call.finish(rc);
@@ -94,20 +126,15 @@ static int matrix_commit_host(const uint64_t *planes, size_t n_rows, size_t n_co
         TRY_CALL(call, F(F_MEMCPY, hipMemcpyAsync(d_pad, pad, (size_t)depth * 32, hipMemcpyHostToDevice, pp.s_k)));
     rc = matrix_hash_rows(call, d_buf, K, planes, n_rows, n_cols, plane_stride, capacity_mont, pad_mode, d_dig);
     if (rc != HADES252_OK) return rc;                                  // (the call is finished already)
-    uint64_t got[4];                                                   // the caller's root is written on success only
-    if (with_tree) {                                                   // the digests never leave the device in between
-        rc = hades252_merkle_build_pad_dev(d_dig, n_rows, arity, tag_mont, out_idx, pad != nullptr ? d_pad : nullptr, d_tree,
-                                           pp.s_k);
-        if (rc != HADES252_OK) return call.finish(rc);
-        if (tree != nullptr)
-            TRY_CALL(call, F(F_MEMCPY, hipMemcpyAsync(tree, d_tree, tree_bytes, hipMemcpyDeviceToHost, pp.s_k)));
-        TRY_CALL(call, F(F_MEMCPY, hipMemcpyAsync(got, d_tree + tree_bytes - 32, 32, hipMemcpyDeviceToHost, pp.s_k)));
-    }
-    if (digests != nullptr)
-        TRY_CALL(call, F(F_MEMCPY, hipMemcpyAsync(digests, d_dig, n_rows * 32, hipMemcpyDeviceToHost, pp.s_k)));
-    TRY_CALL(call, F(F_SYNC, hipStreamSynchronize(pp.s_k)));
-    if (with_tree) memcpy(root, got, 32);
-    return call.finish(HADES252_OK);
+    return matrix_finish(call, d_dig, n_rows, arity, tag_mont, out_idx, pad != nullptr ? d_pad : nullptr, d_tree, digests, tree, root);
+}
+
+// the rules of a commitment's arguments, wherever its rows come from
+static bool matrix_commit_args_ok(size_t n_rows, int pad_mode, int arity, const uint64_t *tag_mont, int out_idx,
+                                  const uint64_t *pad, const uint64_t *digests, const uint64_t *tree, const uint64_t *root) {
+    return hades252_merkle_depth(n_rows, arity) >= 1 && (pad_mode == 0 || pad_mode == 1) && tag_mont != nullptr &&
+           root != nullptr && out_idx >= 0 && out_idx < 5 && !host_misaligned(pad) && !host_misaligned(digests) &&
+           !host_misaligned(tree) && !host_misaligned(root);
 }
 
 int hades252_matrix_row_digests(const uint64_t *planes, size_t n_rows, size_t n_cols, size_t plane_stride,
@@ -123,9 +150,8 @@ int hades252_matrix_row_digests(const uint64_t *planes, size_t n_rows, size_t n_
 int hades252_matrix_commit(const uint64_t *planes, size_t n_rows, size_t n_cols, size_t plane_stride,
                            const uint64_t capacity_mont[4], int pad_mode, int arity, const uint64_t tag_mont[4], int out_idx,
                            const uint64_t *pad, uint64_t *digests, uint64_t *tree, uint64_t root[4]) {
-    if (hades252_merkle_depth(n_rows, arity) < 1 || !matrix_shape_ok(planes, n_rows, n_cols, plane_stride) ||
-        capacity_mont == nullptr || tag_mont == nullptr || root == nullptr || (pad_mode != 0 && pad_mode != 1) || out_idx < 0 ||
-        out_idx >= 5 || host_misaligned(pad) || host_misaligned(digests) || host_misaligned(tree) || host_misaligned(root))
+    if (!matrix_commit_args_ok(n_rows, pad_mode, arity, tag_mont, out_idx, pad, digests, tree, root) ||
+        !matrix_shape_ok(planes, n_rows, n_cols, plane_stride) || capacity_mont == nullptr)
         return HADES252_ERR_INVALID_ARG;
     return matrix_commit_host(planes, n_rows, n_cols, plane_stride, capacity_mont, pad_mode, arity, tag_mont, out_idx, pad,
                               digests, tree, root);
@@ -192,9 +218,8 @@ int hades252_matrix_verify(const uint64_t *rows, size_t n_cols, const uint64_t *
     const size_t rows_bytes = n_queries * n_cols * 32, idx_bytes = n_queries * 8;
     const size_t path_bytes = n_queries * (size_t)depth * (arity - 1) * 32, dig_b = up256(n_queries * 32);
     HostCall call;
-    rc = acquire_pipe(16, call.pipe);
+    rc = call.acquire(16);
     if (rc != HADES252_OK) return rc;
-    call.have_pipe = true;
     HostPipe &pp = call.pipe;
     rc = pipe_ensure_aux(pp, up256(rows_bytes) + up256(idx_bytes) + up256(path_bytes) + 2 * dig_b);
     if (rc != HADES252_OK) return call.finish(rc);

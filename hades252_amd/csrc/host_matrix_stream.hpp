@@ -31,7 +31,9 @@ static size_t mstream_forced_cols() {
     return forced;
 }
 
-static int mstream_device_ok(const MatrixStreamHandle *h) {
+// what every call that touches the device asks first, once its arguments are good: not poisoned, on the stream's device
+static int mstream_enter(const MatrixStreamHandle *h) {
+    if (h->poisoned) return HADES252_ERR_HIP;
     int dev = -1;
     HIP_TRY(hipGetDevice(&dev));
     return dev == h->device ? HADES252_OK : HADES252_ERR_INVALID_ARG;
@@ -40,13 +42,11 @@ static int mstream_device_ok(const MatrixStreamHandle *h) {
 // The group in tiles of K rows x G columns, the measured constants of host_matrix.hpp: K = all rows up to kMatrixFullRows
 // (a full device), G = kMatrixTargetBytes / (32 K) columns, a multiple of four where that leaves at least four -- the first
 // tile is then shortened by the columns of the open block, so that only the first and the last tile of a call carry a
-// partial block.  Tile t + 1 travels (one 2-D copy into a buffer whose plane stride is K) on the copy stream while tile t is
-// absorbed on the kernel stream, with the events of matrix_hash_rows; all kernels are ordered on the kernel stream and the
-// column tiles are the outer loop, so every row sees its columns in order.
+// partial block.  The tiles run through the two-buffer pipeline of host_matrix.hpp (matrix_tile_in, matrix_tile_launched); all
+// kernels are ordered on the kernel stream and the column tiles are the outer loop, so every row sees its columns in order.
 static int mstream_absorb_tiles(MatrixStreamHandle *ms, const uint64_t *planes, size_t n_cols, size_t plane_stride) {
     const size_t S = ms->n_rows;
-    size_t K = matrix_chunk_rows(1);                                   // the test hook's value, else kMatrixFullRows
-    if (K > (S + 255) / 256 * 256) K = (S + 255) / 256 * 256;
+    const size_t K = matrix_tile_rows(1, S);                           // the test hook's value, else kMatrixFullRows
     size_t G = mstream_forced_cols();
     if (G == 0) G = kMatrixTargetBytes / (32 * K);
     if (G < 1) G = 1;
@@ -55,30 +55,24 @@ static int mstream_absorb_tiles(MatrixStreamHandle *ms, const uint64_t *planes, 
     const bool align = G % 4 == 0 && G < n_cols;                       // several tiles of whole blocks: (G >= 4 > cur)
     const size_t buf_b = up256(K * G * 32);
     HostCall call;
-    int rc = acquire_pipe(16, call.pipe);
+    int rc = call.acquire(16);
     if (rc != HADES252_OK) return rc;
-    call.have_pipe = true;
     HostPipe &pp = call.pipe;
     rc = pipe_ensure_aux(pp, 2 * buf_b);
     if (rc != HADES252_OK) return call.finish(rc);
-    const uint8_t *h = (const uint8_t *)planes;
     size_t t = 0;
     unsigned cur = (unsigned)(ms->n_cols % 4);
     for (size_t j = 0; j < n_cols;) {
         size_t gw = j == 0 && align ? G - cur : G;
         if (gw > n_cols - j) gw = n_cols - j;
         for (size_t off = 0; off < S; off += K, t++) {
-            const int k = (int)(t % 2);
             const size_t m = S - off < K ? S - off : K;
-            uint8_t *d = (uint8_t *)pp.aux + (size_t)k * buf_b;
-            if (t >= 2) TRY_CALL(call, F(F_SYNC, hipEventSynchronize(pp.k_done[k])));     // tile t - 2 is absorbed: buffer k is free
-            TRY_CALL(call, F(F_MEMCPY, hipMemcpy2DAsync(d, K * 32, h + (j * plane_stride + off) * 32, plane_stride * 32, m * 32, gw,
-                                                        hipMemcpyHostToDevice, pp.s_in)));
-            TRY_CALL(call, hipEventRecord(pp.in_done[k], pp.s_in));
-            TRY_CALL(call, hipStreamWaitEvent(pp.s_k, pp.in_done[k], 0));
+            uint8_t *d = (uint8_t *)pp.aux + t % 2 * buf_b;
+            rc = matrix_tile_in(call, t, d, K, planes + (j * plane_stride + off) * 4, plane_stride, m, gw);
+            if (rc != HADES252_OK) return rc;
             hipLaunchKernelGGL(k_planes_absorb, dim3(blocks_for(m)), dim3(kBlock), 0, pp.s_k, ms->d_state + off * 32, S, m, d, gw, K, (int)cur);
-            TRY_CALL(call, hipGetLastError());
-            TRY_CALL(call, hipEventRecord(pp.k_done[k], pp.s_k));
+            rc = matrix_tile_launched(call, t);
+            if (rc != HADES252_OK) return rc;
         }
         j += gw;
         cur = (unsigned)((cur + gw) % 4);
@@ -93,8 +87,7 @@ static int mstream_finish(MatrixStreamHandle *ms, int pad_mode, int arity, const
     const size_t S = ms->n_rows;
     const bool with_tree = root != nullptr;
     const int depth = with_tree ? hades252_merkle_depth(S, arity) : 0;
-    const size_t tree_bytes = with_tree ? hades252_merkle_tree_bytes(S, arity) : 0;
-    const size_t tree_b = up256(tree_bytes), pad_b = up256((size_t)depth * 32);
+    const size_t tree_b = up256(with_tree ? hades252_merkle_tree_bytes(S, arity) : 0), pad_b = up256((size_t)depth * 32);
     if (ms->d_dig == nullptr) HIP_TRY(F(F_MALLOC, hipMalloc((void **)&ms->d_dig, up256(S * 32))));
     if (with_tree && ms->tree_cap < tree_b + pad_b) {
         if (ms->d_tree) (void)hipFree(ms->d_tree);
@@ -105,28 +98,14 @@ static int mstream_finish(MatrixStreamHandle *ms, int pad_mode, int arity, const
     }
     uint8_t *d_pad = with_tree ? ms->d_tree + tree_b : nullptr;
     HostCall call;
-    int rc = acquire_pipe(16, call.pipe);
+    int rc = call.acquire(16);
     if (rc != HADES252_OK) return rc;
-    call.have_pipe = true;
     HostPipe &pp = call.pipe;
     if (with_tree && pad != nullptr)
         TRY_CALL(call, F(F_MEMCPY, hipMemcpyAsync(d_pad, pad, (size_t)depth * 32, hipMemcpyHostToDevice, pp.s_k)));
     hipLaunchKernelGGL(k_planes_finish, dim3(blocks_for(S)), dim3(kBlock), 0, pp.s_k, ms->d_state, S, S, ms->d_dig, (int)(ms->n_cols % 4), pad_mode);
     TRY_CALL(call, hipGetLastError());
-    uint64_t got[4];                                                   // the caller's root is written on success only
-    if (with_tree) {                                                   // the digests never leave the device in between
-        rc = hades252_merkle_build_pad_dev(ms->d_dig, S, arity, tag_mont, out_idx, pad != nullptr ? d_pad : nullptr, ms->d_tree,
-                                           pp.s_k);
-        if (rc != HADES252_OK) return call.finish(rc);
-        if (tree != nullptr)
-            TRY_CALL(call, F(F_MEMCPY, hipMemcpyAsync(tree, ms->d_tree, tree_bytes, hipMemcpyDeviceToHost, pp.s_k)));
-        TRY_CALL(call, F(F_MEMCPY, hipMemcpyAsync(got, ms->d_tree + tree_bytes - 32, 32, hipMemcpyDeviceToHost, pp.s_k)));
-    }
-    if (digests != nullptr)
-        TRY_CALL(call, F(F_MEMCPY, hipMemcpyAsync(digests, ms->d_dig, S * 32, hipMemcpyDeviceToHost, pp.s_k)));
-    TRY_CALL(call, F(F_SYNC, hipStreamSynchronize(pp.s_k)));
-    if (with_tree) memcpy(root, got, 32);
-    return call.finish(HADES252_OK);
+    return matrix_finish(call, ms->d_dig, S, arity, tag_mont, out_idx, pad != nullptr ? d_pad : nullptr, ms->d_tree, digests, tree, root);
 }
 
 // (a failure with HADES252_ERR_HIP leaves the state planes, or the streams they were written on, in an unknown condition)
@@ -162,9 +141,8 @@ int hades252_matstream_open(void **out, size_t n_rows, const uint64_t capacity_m
         HIP_TRY(hipGetDevice(&ms->device));
         HIP_TRY(F(F_MALLOC, hipMalloc((void **)&ms->d_state, n_rows * 160)));
         HostCall call;
-        int r = acquire_pipe(16, call.pipe);
+        int r = call.acquire(16);
         if (r != HADES252_OK) return r;
-        call.have_pipe = true;
         hipLaunchKernelGGL(k_planes_init, dim3(blocks_for(n_rows)), dim3(kBlock), 0, call.pipe.s_k, ms->d_state, n_rows, n_rows,
                            fr_from_u64(capacity_mont));
         TRY_CALL(call, hipGetLastError());
@@ -187,8 +165,7 @@ int hades252_matstream_absorb(void *ms, const uint64_t *planes, size_t n_cols, s
     if (planes == nullptr || host_misaligned(planes) || plane_stride < h->n_rows || plane_stride > SIZE_MAX / 32 / n_cols ||
         (uint64_t)n_cols > UINT64_MAX - h->n_cols)
         return HADES252_ERR_INVALID_ARG;
-    if (h->poisoned) return HADES252_ERR_HIP;
-    int rc = mstream_device_ok(h);
+    int rc = mstream_enter(h);
     if (rc != HADES252_OK) return rc;
     rc = mstream_poison_on_hip(h, mstream_absorb_tiles(h, planes, n_cols, plane_stride));
     if (rc == HADES252_OK) h->n_cols += n_cols;
@@ -205,8 +182,7 @@ int hades252_matstream_digests(void *ms, int pad_mode, uint64_t *digests) {
     MatrixStreamHandle *h = (MatrixStreamHandle *)ms;
     if (h == nullptr || h->n_cols == 0 || (pad_mode != 0 && pad_mode != 1) || digests == nullptr || host_misaligned(digests))
         return HADES252_ERR_INVALID_ARG;
-    if (h->poisoned) return HADES252_ERR_HIP;
-    int rc = mstream_device_ok(h);
+    const int rc = mstream_enter(h);
     if (rc != HADES252_OK) return rc;
     return mstream_poison_on_hip(h, mstream_finish(h, pad_mode, 0, nullptr, 0, nullptr, digests, nullptr, nullptr));
 }
@@ -214,12 +190,9 @@ int hades252_matstream_digests(void *ms, int pad_mode, uint64_t *digests) {
 int hades252_matstream_commit(void *ms, int pad_mode, int arity, const uint64_t tag_mont[4], int out_idx, const uint64_t *pad,
                               uint64_t *digests, uint64_t *tree, uint64_t root[4]) {
     MatrixStreamHandle *h = (MatrixStreamHandle *)ms;
-    if (h == nullptr || h->n_cols == 0 || (pad_mode != 0 && pad_mode != 1) || hades252_merkle_depth(h->n_rows, arity) < 1 ||
-        tag_mont == nullptr || root == nullptr || out_idx < 0 || out_idx >= 5 || host_misaligned(pad) ||
-        host_misaligned(digests) || host_misaligned(tree) || host_misaligned(root))
+    if (h == nullptr || h->n_cols == 0 || !matrix_commit_args_ok(h->n_rows, pad_mode, arity, tag_mont, out_idx, pad, digests, tree, root))
         return HADES252_ERR_INVALID_ARG;
-    if (h->poisoned) return HADES252_ERR_HIP;
-    int rc = mstream_device_ok(h);
+    const int rc = mstream_enter(h);
     if (rc != HADES252_OK) return rc;
     return mstream_poison_on_hip(h, mstream_finish(h, pad_mode, arity, tag_mont, out_idx, pad, digests, tree, root));
 }

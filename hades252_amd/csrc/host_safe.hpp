@@ -20,9 +20,8 @@ int hades252_safe_hash(const uint64_t *in, size_t n_msgs, const uint32_t *calls,
     if (chunk > kMaxLaunchRecords) chunk = kMaxLaunchRecords;
     const size_t in_b = chunk * plan.n_in * 32, out_b = chunk * plan.n_out * 32;
     HostCall call;
-    rc = acquire_pipe(16, call.pipe);
+    rc = call.acquire(16);
     if (rc != HADES252_OK) return rc;
-    call.have_pipe = true;
     HostPipe &pp = call.pipe;
     rc = pipe_ensure_aux(pp, in_b + out_b + 16);
     if (rc != HADES252_OK) return call.finish(rc);

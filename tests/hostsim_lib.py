@@ -216,6 +216,50 @@ def build(variant: str = "asan", part: str = "perm", mutant=None, verbose: bool 
     return exe
 
 
+def build_driver(main_path: str, name: str, variant: str = "asan") -> str:
+    """-> path of <directory of main_path>/build/<name>: a stand-alone driver (its own main) over the stand-in header and the
+    copied tree, under FLAGS[variant]; rebuilt when the driver, the stand-in, a copied header or the flags change."""
+    texts = {rel: rewritten(rel) for rel in COPIED}
+    check_copy(texts)
+    with open(main_path) as f:
+        included = re.findall(r'^#include "((?:include|hades252_amd)/[^"]+)"', f.read(), flags=re.M)
+    assert set(included) <= set(texts)
+    h = hashlib.sha256(" ".join(FLAGS[variant] + COMMON).encode())
+    for path in (main_path, STANDIN):
+        with open(path, "rb") as f:
+            h.update(f.read())
+    for rel in sorted(texts):
+        h.update(rel.encode() + b"\0" + texts[rel].encode())
+    want = h.hexdigest()
+    out_dir = os.path.join(os.path.dirname(main_path), "build")
+    os.makedirs(out_dir, exist_ok=True)
+    out, stamp = os.path.join(out_dir, name), os.path.join(out_dir, name + ".stamp")
+
+    def fresh():
+        return os.path.exists(out) and os.path.exists(stamp) and open(stamp).read().strip() == want
+
+    with open(os.path.join(out_dir, name + ".lock"), "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        try:
+            if not fresh():
+                src = os.path.join(out_dir, "src")
+                for rel, text in texts.items():
+                    os.makedirs(os.path.dirname(os.path.join(src, rel)), exist_ok=True)
+                    with open(os.path.join(src, rel), "w") as f:
+                        f.write(text)
+                tmp = out + ".tmp.%d" % os.getpid()
+                r = subprocess.run([CLANG] + COMMON + FLAGS[variant] + ["-I", HOSTSIM, "-I", src, main_path, "-o", tmp],
+                                   capture_output=True, text=True)
+                assert r.returncode == 0, r.stderr[-8000:]
+                os.replace(tmp, out)
+                with open(stamp + ".tmp", "w") as f:
+                    f.write(want + "\n")
+                os.replace(stamp + ".tmp", stamp)
+        finally:
+            fcntl.flock(lock, fcntl.LOCK_UN)
+    return out
+
+
 # every executable the tests use: (variant, part, mutant).  TSan runs the perm, merkle and sponge parts; the mutants live
 # in the perm part (k_perm_fast through the shipped launcher, and the unit wrappers).
 MUTANT_VARIANT = {"store_off_by_one": "asan", "lds_halved": "asan", "load_barrier_removed": "tsan", "negp_index": "asan",

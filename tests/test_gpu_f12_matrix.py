@@ -170,6 +170,34 @@ def test_commit(hades_lib, oracle, pool, arity):
             assert commit(False, False)[2].tobytes() == root.tobytes()
 
 
+def test_a_failing_copy_fails_the_commit_leaves_the_root_alone_and_loses_no_pipe(hades_lib, H, oracle, pool):
+    """hades252_fault_inject returns an error INSTEAD of making the call: no GPU work is disturbed.  "memcpy:1" is the 2-D
+    copy of the first tile (no padding table travels in front of it)."""
+    n_rows, n_cols = 300, 5
+    sub = np.ascontiguousarray(pool[0][:n_rows, :n_cols])
+    planes = M.planes_of(sub)
+
+    def commit(root):
+        return hades_lib.hades252_matrix_commit(_p(planes), n_rows, n_cols, planes.shape[1], _cap(), 1, 2, _tag(2), 1, None, None,
+                                                None, _p(root))
+
+    H.trim()                                                              # the pool holds this call's pipe and nothing else
+    first = np.zeros(4, dtype=np.uint64)
+    assert commit(first) == 0
+    held = H.pool_bytes()
+    assert held > 0
+    root = np.full(4, SENTINEL, dtype=np.uint64)
+    H.fault_inject("memcpy:1")
+    try:
+        assert commit(root) == -2                                         # HADES252_ERR_HIP
+    finally:
+        H.fault_inject(None)
+    assert (root == SENTINEL).all()
+    assert commit(root) == 0
+    assert root.tobytes() == first.tobytes() == M.commit(oracle, sub, 2)[2].tobytes()
+    assert H.pool_bytes() == held
+
+
 # ---- 5. several chunks -------------------------------------------------------------------------------------------------
 _CHUNK_CHILD = r"""
 import os, sys

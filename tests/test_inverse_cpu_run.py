@@ -6,8 +6,6 @@ tests/hostsim/hip/hip_runtime.h and the tree's headers as tests/hostsim_lib.py c
 semantically empty edits; check_copy() refuses anything else).  It is built with hostsim_lib's compiler and its "asan" flags
 and run as an ordinary child process on heap buffers of exactly the data's size: nothing is preloaded, nothing is loaded
 into this interpreter.  An emulated block takes seconds, so the cases are few."""
-import fcntl
-import hashlib
 import os
 import re
 import subprocess
@@ -23,54 +21,13 @@ import perm_inverse_model as M  # noqa: E402
 
 HERE = os.path.join(ROOT, "tests", "hostsim_inverse")
 MAIN = os.path.join(HERE, "inverse_main.cpp")
-BUILD = os.path.join(HERE, "build")
 S, P = M.S, M.P
-
-
-def _included():
-    with open(MAIN) as f:
-        return re.findall(r'^#include "((?:include|hades252_amd)/[^"]+)"', f.read(), flags=re.M)
 
 
 @pytest.fixture(scope="module")
 def exe():
     """The driver under ASan + UBSan; rebuilt when the driver, the stand-in, a copied header or the flags change."""
-    texts = {rel: HS.rewritten(rel) for rel in HS.COPIED}
-    HS.check_copy(texts)
-    assert set(_included()) <= set(texts)
-    h = hashlib.sha256(" ".join(HS.FLAGS["asan"] + HS.COMMON).encode())
-    for path in (MAIN, HS.STANDIN):
-        with open(path, "rb") as f:
-            h.update(f.read())
-    for rel in sorted(texts):
-        h.update(rel.encode() + b"\0" + texts[rel].encode())
-    want = h.hexdigest()
-    os.makedirs(BUILD, exist_ok=True)
-    out, stamp = os.path.join(BUILD, "inverse_main"), os.path.join(BUILD, "inverse_main.stamp")
-
-    def fresh():
-        return os.path.exists(out) and os.path.exists(stamp) and open(stamp).read().strip() == want
-
-    with open(os.path.join(BUILD, "inverse_main.lock"), "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        try:
-            if not fresh():
-                src = os.path.join(BUILD, "src")
-                for rel, text in texts.items():
-                    os.makedirs(os.path.dirname(os.path.join(src, rel)), exist_ok=True)
-                    with open(os.path.join(src, rel), "w") as f:
-                        f.write(text)
-                tmp = out + ".tmp.%d" % os.getpid()
-                r = subprocess.run([HS.CLANG] + HS.COMMON + HS.FLAGS["asan"] + ["-I", HS.HOSTSIM, "-I", src, MAIN, "-o", tmp],
-                                   capture_output=True, text=True)
-                assert r.returncode == 0, r.stderr[-8000:]
-                os.replace(tmp, out)
-                with open(stamp + ".tmp", "w") as f:
-                    f.write(want + "\n")
-                os.replace(stamp + ".tmp", stamp)
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
-    return out
+    return HS.build_driver(MAIN, "inverse_main")
 
 
 def _run(exe, tmp_path, what, data, n, *rounds):

@@ -8,8 +8,6 @@ and run as an ordinary child process: nothing is preloaded, nothing is loaded in
 block that ends with the last row of the last plane, the gaps between planes are poisoned, the digests are a heap block of
 exactly n_rows * 32 bytes: a read past a plane's last row or a store past the last digest is an ASan report.  An emulated
 block takes seconds, so the cases are few."""
-import fcntl
-import hashlib
 import os
 import re
 import subprocess
@@ -27,53 +25,12 @@ from gpu_common import CAP  # noqa: E402
 
 HERE = os.path.join(ROOT, "tests", "hostsim_matrix")
 MAIN = os.path.join(HERE, "matrix_main.cpp")
-BUILD = os.path.join(HERE, "build")
-
-
-def _included():
-    with open(MAIN) as f:
-        return re.findall(r'^#include "((?:include|hades252_amd)/[^"]+)"', f.read(), flags=re.M)
 
 
 @pytest.fixture(scope="module")
 def exe():
     """The driver under ASan + UBSan; rebuilt when the driver, the stand-in, a copied header or the flags change."""
-    texts = {rel: HS.rewritten(rel) for rel in HS.COPIED}
-    HS.check_copy(texts)
-    assert set(_included()) <= set(texts)
-    h = hashlib.sha256(" ".join(HS.FLAGS["asan"] + HS.COMMON).encode())
-    for path in (MAIN, HS.STANDIN):
-        with open(path, "rb") as f:
-            h.update(f.read())
-    for rel in sorted(texts):
-        h.update(rel.encode() + b"\0" + texts[rel].encode())
-    want = h.hexdigest()
-    os.makedirs(BUILD, exist_ok=True)
-    out, stamp = os.path.join(BUILD, "matrix_main"), os.path.join(BUILD, "matrix_main.stamp")
-
-    def fresh():
-        return os.path.exists(out) and os.path.exists(stamp) and open(stamp).read().strip() == want
-
-    with open(os.path.join(BUILD, "matrix_main.lock"), "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        try:
-            if not fresh():
-                src = os.path.join(BUILD, "src")
-                for rel, text in texts.items():
-                    os.makedirs(os.path.dirname(os.path.join(src, rel)), exist_ok=True)
-                    with open(os.path.join(src, rel), "w") as f:
-                        f.write(text)
-                tmp = out + ".tmp.%d" % os.getpid()
-                r = subprocess.run([HS.CLANG] + HS.COMMON + HS.FLAGS["asan"] + ["-I", HS.HOSTSIM, "-I", src, MAIN, "-o", tmp],
-                                   capture_output=True, text=True)
-                assert r.returncode == 0, r.stderr[-8000:]
-                os.replace(tmp, out)
-                with open(stamp + ".tmp", "w") as f:
-                    f.write(want + "\n")
-                os.replace(stamp + ".tmp", stamp)
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
-    return out
+    return HS.build_driver(MAIN, "matrix_main")
 
 
 def _exact_planes(matrix, stride):
