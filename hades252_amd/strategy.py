@@ -35,13 +35,11 @@ from typing import Iterator
 
 import numpy as np
 
-from . import _lib
+from . import PARTIAL_ROUNDS, TOTAL_FULL_ROUNDS, WIDTH, _lib
 from ._lib import check
 
-WIDTH = 5
-TOTAL_FULL_ROUNDS = 8
-PARTIAL_ROUNDS = 59
 STATE_BYTES = WIDTH * 32
+ROUNDS_TOTAL = TOTAL_FULL_ROUNDS + PARTIAL_ROUNDS          # HADES252_ROUNDS_TOTAL, src/strategies.rs:160-162
 N_ROUND_CONSTANTS = 960          # src/round_constants.rs:18 (335 are ever consumed)
 
 
@@ -62,10 +60,7 @@ class RoundConstantsIter:
         return self.pos - 1
 
 
-def _is_torch(x) -> bool:
-    return type(x).__module__.startswith("torch")
-
-
+# ---- the device path: torch is imported here, on first use, never at module import (see the RATE WARNING above) -------
 def _dev_buffer(x, unit_bytes: int, what: str):
     """-> (data_ptr, n_units, torch device) of a contiguous CUDA tensor."""
     import torch
@@ -87,6 +82,64 @@ def _dev_buffer(x, unit_bytes: int, what: str):
 def _stream_ptr(device) -> int:
     import torch
     return torch.cuda.current_stream(device).cuda_stream
+
+
+def _dev_call(where: str, dev, fn_name: str, *args, after=()) -> None:
+    """The one way into a ``_dev`` entry point of the library: with ``dev`` current and on torch's current stream there.
+    The stream follows ``args``; ``after`` is what an ``_ex`` signature still takes behind it."""
+    import torch
+    with torch.cuda.device(dev):
+        check(getattr(_lib.lib(), fn_name)(*args, _stream_ptr(dev), *after), where)
+
+
+def _dev_empty(dev, *shape, dtype: str = "int64"):
+    import torch
+    return torch.empty(shape, dtype=getattr(torch, dtype), device=dev)
+
+
+def _dev_counter(dev):
+    """One zeroed int32 the library counts into (rejected messages, indices out of range, ...)."""
+    import torch
+    return torch.zeros(1, dtype=torch.int32, device=dev)
+
+
+def _witness_pair(dev, steps: int, n: int):
+    """(wires [972, steps, n, 4], inputs [steps, n, 5, 4]): the two record buffers of a chain witness."""
+    return _dev_empty(dev, witness_wires(), steps, n, 4), _dev_empty(dev, steps, n, WIDTH, 4)
+
+
+# ---- the host path ---------------------------------------------------------------------------------------------------------
+def _ptr(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _host_u64(a, what: str, tail: tuple | None = None) -> np.ndarray:
+    """Type and contiguity of a host batch and, when ``tail`` is given, its shape [n, *tail]."""
+    if not isinstance(a, np.ndarray) or a.dtype != np.uint64 or not a.flags.c_contiguous:
+        raise TypeError("%s: host buffers must be C-contiguous numpy uint64" % what)
+    if tail is not None and (a.ndim != 1 + len(tail) or a.shape[1:] != tail):
+        raise ValueError("%s: the input must have shape [n, %s], got %r" % (what, ", ".join(map(str, tail)), a.shape))
+    return a
+
+
+def _host_units(a, what: str, limbs: int = 4) -> int:
+    """How many units of ``limbs`` uint64 (4: a scalar, 20: a state) a valid host batch holds."""
+    if _host_u64(a, what).size % limbs:
+        raise ValueError("%s: %d limbs is not a whole number of %d-limb units" % (what, a.size, limbs))
+    return a.size // limbs
+
+
+def _host_pad(where: str, pad, depth: int):
+    """The pointer of a host padding table [depth, 4], None for None."""
+    if pad is None:
+        return None
+    if _host_u64(pad, where).size != depth * 4:
+        raise ValueError("%s: the padding table needs %d digests" % (where, depth))
+    return _ptr(pad)
+
+
+def _tag_arr(tag_mont: int):
+    return (ctypes.c_uint64 * 4)(*[(tag_mont >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(4)])
 
 
 class Strategy:
@@ -123,7 +176,7 @@ class Strategy:
     @staticmethod
     def rounds() -> int:
         """src/strategies.rs:160-162."""
-        return TOTAL_FULL_ROUNDS + PARTIAL_ROUNDS
+        return ROUNDS_TOTAL
 
 
 class ScalarStrategy(Strategy):
@@ -147,64 +200,48 @@ class ScalarStrategy(Strategy):
             raise RuntimeError("Hades252 out of ARK constants")
         return constants.pos
 
-    def add_round_key(self, constants: RoundConstantsIter, words) -> None:
-        """src/strategies/scalar.rs:23-30: word w of every state += next_c()."""
-        import torch
-        ptr, n, dev = _dev_buffer(words, STATE_BYTES, "add_round_key")
-        cur = self._cursor_of(constants)
-        with torch.cuda.device(dev):
-            check(_lib.lib().hades252_add_round_key_at_dev(ptr, n, cur, _stream_ptr(dev)), "add_round_key")
+    def _round_at_cursor(self, op: str, constants: RoundConstantsIter, words) -> None:
+        """``hades252_<op>_at_dev`` on every state of ``words``; the cursor moves on by WIDTH constants."""
+        ptr, n, dev = _dev_buffer(words, STATE_BYTES, op)
+        _dev_call(op, dev, "hades252_%s_at_dev" % op, ptr, n, self._cursor_of(constants))
         for _ in range(WIDTH):
             self.next_c(constants)
+
+    def add_round_key(self, constants: RoundConstantsIter, words) -> None:
+        """src/strategies/scalar.rs:23-30: word w of every state += next_c()."""
+        self._round_at_cursor("add_round_key", constants, words)
 
     def quintic_s_box(self, value) -> None:
         """src/strategies/scalar.rs:32-34 on every 32-byte scalar of ``value``."""
-        import torch
         ptr, n, dev = _dev_buffer(value, 32, "quintic_s_box")
-        with torch.cuda.device(dev):
-            check(_lib.lib().hades252_quintic_s_box_dev(ptr, n, _stream_ptr(dev)), "quintic_s_box")
+        _dev_call("quintic_s_box", dev, "hades252_quintic_s_box_dev", ptr, n)
 
     def mul_matrix(self, constants: RoundConstantsIter, values) -> None:
         """src/strategies/scalar.rs:36-49 (``_constants`` is unused there too)."""
-        import torch
         ptr, n, dev = _dev_buffer(values, STATE_BYTES, "mul_matrix")
-        with torch.cuda.device(dev):
-            check(_lib.lib().hades252_mul_matrix_dev(ptr, n, _stream_ptr(dev)), "mul_matrix")
+        _dev_call("mul_matrix", dev, "hades252_mul_matrix_dev", ptr, n)
 
     def apply_partial_round(self, constants: RoundConstantsIter, words) -> None:
         """src/strategies.rs:79-93, fused in one launch."""
-        import torch
-        ptr, n, dev = _dev_buffer(words, STATE_BYTES, "apply_partial_round")
-        cur = self._cursor_of(constants)
-        with torch.cuda.device(dev):
-            check(_lib.lib().hades252_apply_partial_round_at_dev(ptr, n, cur, _stream_ptr(dev)), "apply_partial_round")
-        for _ in range(WIDTH):
-            self.next_c(constants)
+        self._round_at_cursor("apply_partial_round", constants, words)
 
     def apply_full_round(self, constants: RoundConstantsIter, words) -> None:
         """src/strategies.rs:107-119, fused in one launch."""
-        import torch
-        ptr, n, dev = _dev_buffer(words, STATE_BYTES, "apply_full_round")
-        cur = self._cursor_of(constants)
-        with torch.cuda.device(dev):
-            check(_lib.lib().hades252_apply_full_round_at_dev(ptr, n, cur, _stream_ptr(dev)), "apply_full_round")
-        for _ in range(WIDTH):
-            self.next_c(constants)
+        self._round_at_cursor("apply_full_round", constants, words)
 
     def perm(self, data) -> None:
         """src/strategies.rs:140-157 on every state of ``data``, in place."""
         if isinstance(data, np.ndarray):
-            if data.dtype != np.uint64 or not data.flags["C_CONTIGUOUS"]:
+            # the one host batch that is checked and pointed at inline, beside _host_u64 and _ptr: single-call timings
+            # (bench.py single_perm, tools/small_call_latency.py) see every Python call made between here and the library
+            if data.dtype != np.uint64 or not data.flags.c_contiguous:
                 raise TypeError("perm: host buffers must be C-contiguous numpy uint64")
             if data.size % (WIDTH * 4) != 0:
                 raise ValueError("perm: %d limbs is not a whole number of %d-word states" % (data.size, WIDTH))
-            check(_lib.lib().hades252_perm_batch(data.ctypes.data_as(ctypes.c_void_p), data.size // (WIDTH * 4)),
-                  "perm")
+            check(_lib.lib().hades252_perm_batch(data.ctypes.data_as(ctypes.c_void_p), data.size // (WIDTH * 4)), "perm")
             return
-        import torch
         ptr, n, dev = _dev_buffer(data, STATE_BYTES, "perm")
-        with torch.cuda.device(dev):
-            check(_lib.lib().hades252_perm_batch_dev_ex(ptr, n, _stream_ptr(dev), self.kernel), "perm")
+        _dev_call("perm", dev, "hades252_perm_batch_dev_ex", ptr, n, after=(self.kernel,))
 
     def perm_stepwise(self, data) -> None:
         """The provided ``perm`` body of the trait written out over the per-round entry points
@@ -284,52 +321,33 @@ class HostBuffer:
 
 def host_register(arr: np.ndarray) -> None:
     """Page-lock an existing host array in place, once (``hades252_host_register``)."""
-    check(_lib.lib().hades252_host_register(arr.ctypes.data_as(ctypes.c_void_p), arr.nbytes), "host_register")
+    check(_lib.lib().hades252_host_register(_ptr(arr), arr.nbytes), "host_register")
 
 
 def host_unregister(arr: np.ndarray) -> None:
-    check(_lib.lib().hades252_host_unregister(arr.ctypes.data_as(ctypes.c_void_p)), "host_unregister")
+    check(_lib.lib().hades252_host_unregister(_ptr(arr)), "host_unregister")
 
 
 def host_is_pinned(arr: np.ndarray) -> bool:
-    return bool(_lib.lib().hades252_host_is_pinned(arr.ctypes.data_as(ctypes.c_void_p), arr.nbytes))
+    return bool(_lib.lib().hades252_host_is_pinned(_ptr(arr), arr.nbytes))
 
 
 def perm_multi(data: np.ndarray, n_workers: int = 0, virtual: bool = False) -> None:
     """``hades252_perm_batch_multi_ex``: a host batch sharded over n_workers host threads / devices (0 = every
     visible device), contiguous range per worker, no collective.  ``virtual``: worker g runs on device
     g % device_count, so n_workers may exceed the number of GPUs."""
-    if data.dtype != np.uint64 or not data.flags["C_CONTIGUOUS"]:
-        raise TypeError("perm_multi: host buffers must be C-contiguous numpy uint64")
-    if data.size % (WIDTH * 4) != 0:
-        raise ValueError("perm_multi: %d limbs is not a whole number of %d-word states" % (data.size, WIDTH))
-    check(_lib.lib().hades252_perm_batch_multi_ex(data.ctypes.data_as(ctypes.c_void_p), data.size // (WIDTH * 4),
-                                                  n_workers, _lib.MULTI_VIRTUAL if virtual else 0), "perm_multi")
-
-
-def _host_u64(a, what: str) -> np.ndarray:
-    if not isinstance(a, np.ndarray) or a.dtype != np.uint64 or not a.flags["C_CONTIGUOUS"]:
-        raise TypeError("%s: host buffers must be C-contiguous numpy uint64" % what)
-    return a
+    n = _host_units(data, "perm_multi", WIDTH * 4)
+    check(_lib.lib().hades252_perm_batch_multi_ex(_ptr(data), n, n_workers, _lib.MULTI_VIRTUAL if virtual else 0), "perm_multi")
 
 
 def merkle_root_host(leaves: np.ndarray, arity: int, tag_mont: int, out_idx: int = 1, pad: np.ndarray | None = None) -> np.ndarray:
     """``hades252_merkle_root``: root (4 limbs) of the tree over leaves held in HOST memory (n x 4 uint64); the leaves travel
     to the device in chunks while the first tree level is hashed behind them.  ``pad``: host table [depth, 4] or None."""
-    leaves = _host_u64(leaves, "merkle_root_host")
-    if leaves.size % 4:
-        raise ValueError("merkle_root_host: %d limbs is not a whole number of scalars" % leaves.size)
-    n = leaves.size // 4
-    depth = merkle_depth(n, arity, "merkle_root_host")
-    pptr = None
-    if pad is not None:
-        pad = _host_u64(pad, "merkle_root_host")
-        if pad.size != depth * 4:
-            raise ValueError("merkle_root_host: the padding table needs %d digests" % depth)
-        pptr = pad.ctypes.data_as(ctypes.c_void_p)
+    n = _host_units(leaves, "merkle_root_host")
+    pptr = _host_pad("merkle_root_host", pad, merkle_depth(n, arity, "merkle_root_host"))
     root = np.zeros(4, dtype=np.uint64)
-    check(_lib.lib().hades252_merkle_root(leaves.ctypes.data_as(ctypes.c_void_p), n, arity, _tag_arr(tag_mont), out_idx,
-                                          pptr, root.ctypes.data_as(ctypes.c_void_p)), "merkle_root_host")
+    check(_lib.lib().hades252_merkle_root(_ptr(leaves), n, arity, _tag_arr(tag_mont), out_idx, pptr, _ptr(root)),
+          "merkle_root_host")
     return root
 
 
@@ -338,10 +356,8 @@ def merkle_root_multi(leaves: np.ndarray, arity: int, tag_mont: int, out_idx: in
     n_workers devices (0 = all visible); ``virtual``: worker g on device g % device_count."""
     leaves = _host_u64(leaves, "merkle_root_multi")
     root = np.zeros(4, dtype=np.uint64)
-    check(_lib.lib().hades252_merkle_root_multi(leaves.ctypes.data_as(ctypes.c_void_p), leaves.size // 4, arity,
-                                                _tag_arr(tag_mont), out_idx, n_workers,
-                                                _lib.MULTI_VIRTUAL if virtual else 0, root.ctypes.data_as(ctypes.c_void_p)),
-          "merkle_root_multi")
+    check(_lib.lib().hades252_merkle_root_multi(_ptr(leaves), leaves.size // 4, arity, _tag_arr(tag_mont), out_idx, n_workers,
+                                                _lib.MULTI_VIRTUAL if virtual else 0, _ptr(root)), "merkle_root_multi")
     return root
 
 
@@ -351,9 +367,8 @@ def sponge_hash_host(msgs: np.ndarray, n_msgs: int, msg_len: int, capacity_mont:
     if msgs.size != n_msgs * msg_len * 4:
         raise ValueError("sponge_hash_host: buffer is not %d messages of %d scalars" % (n_msgs, msg_len))
     out = np.zeros((n_msgs, 4), dtype=np.uint64)
-    check(_lib.lib().hades252_sponge_hash(msgs.ctypes.data_as(ctypes.c_void_p) if msgs.size else None, n_msgs, msg_len,
-                                          _tag_arr(capacity_mont), pad_mode, out.ctypes.data_as(ctypes.c_void_p)),
-          "sponge_hash_host")
+    check(_lib.lib().hades252_sponge_hash(_ptr(msgs) if msgs.size else None, n_msgs, msg_len, _tag_arr(capacity_mont), pad_mode,
+                                          _ptr(out)), "sponge_hash_host")
     return out
 
 
@@ -365,42 +380,37 @@ def sponge_hash_var_host(scalars: np.ndarray, offsets: np.ndarray, lengths: np.n
     n = offsets.size
     out = np.zeros((n, 4), dtype=np.uint64)
     bad = ctypes.c_size_t(0)
-    check(_lib.lib().hades252_sponge_hash_var(scalars.ctypes.data_as(ctypes.c_void_p) if scalars.size else None, scalars.size // 4,
-                                              offsets.ctypes.data_as(ctypes.c_void_p), lengths.ctypes.data_as(ctypes.c_void_p),
-                                              n, _tag_arr(capacity_mont), pad_mode, out.ctypes.data_as(ctypes.c_void_p),
-                                              ctypes.byref(bad)), "sponge_hash_var_host")
+    check(_lib.lib().hades252_sponge_hash_var(_ptr(scalars) if scalars.size else None, scalars.size // 4, _ptr(offsets),
+                                              _ptr(lengths), n, _tag_arr(capacity_mont), pad_mode, _ptr(out), ctypes.byref(bad)),
+          "sponge_hash_var_host")
     return out, int(bad.value)
+
+
+def _trace(where: str, fn_name: str, states_t, out, after=()):
+    ptr, n, dev = _dev_buffer(states_t, STATE_BYTES, where)
+    trace = _dev_empty(dev, ROUNDS_TOTAL, n, WIDTH, 4) if out is None else out
+    _dev_call(where, dev, fn_name, ptr, trace.data_ptr(), n, after=after)
+    return trace
 
 
 def perm_trace(states_t, kernel: int = _lib.KERNEL_DEFAULT, out=None):
     """State after every round (round-major: result[r] is the batch after round r); the input is
     left untouched.  Witness pre-computation for the reference's GadgetStrategy
     (src/strategies/gadget.rs:41-133)."""
-    import torch
-    ptr, n, dev = _dev_buffer(states_t, STATE_BYTES, "perm_trace")
-    trace = torch.empty((Strategy.rounds(), n, WIDTH, 4), dtype=torch.int64, device=dev) if out is None else out
-    with torch.cuda.device(dev):
-        check(_lib.lib().hades252_perm_trace_dev_ex(ptr, trace.data_ptr(), n, _stream_ptr(dev), kernel), "perm_trace")
-    return trace
+    return _trace("perm_trace", "hades252_perm_trace_dev_ex", states_t, out, (kernel,))
 
 
 def perm_trace_scaled(states_t, out=None):
     """The per-round trace in SCALED form (include/hades252.h: hades252_perm_trace_scaled_dev): same shape as
     ``perm_trace``; ``true[r][w] = scaled[r][w] * mul[r] + add[r][w]`` with the tables of ``trace_scale_table()``."""
-    import torch
-    ptr, n, dev = _dev_buffer(states_t, STATE_BYTES, "perm_trace_scaled")
-    trace = torch.empty((Strategy.rounds(), n, WIDTH, 4), dtype=torch.int64, device=dev) if out is None else out
-    with torch.cuda.device(dev):
-        check(_lib.lib().hades252_perm_trace_scaled_dev(ptr, trace.data_ptr(), n, _stream_ptr(dev)), "perm_trace_scaled")
-    return trace
+    return _trace("perm_trace_scaled", "hades252_perm_trace_scaled_dev", states_t, out)
 
 
 def trace_scale_table():
     """(mul [67, 4], add [67, 5, 4]) uint64 numpy arrays: in-memory BlsScalar limbs (host tables, no device call)."""
-    mul = np.zeros((Strategy.rounds(), 4), dtype=np.uint64)
-    add = np.zeros((Strategy.rounds(), WIDTH, 4), dtype=np.uint64)
-    check(_lib.lib().hades252_perm_trace_scale_table(mul.ctypes.data_as(ctypes.c_void_p), add.ctypes.data_as(ctypes.c_void_p)),
-          "trace_scale_table")
+    mul = np.zeros((ROUNDS_TOTAL, 4), dtype=np.uint64)
+    add = np.zeros((ROUNDS_TOTAL, WIDTH, 4), dtype=np.uint64)
+    check(_lib.lib().hades252_perm_trace_scale_table(_ptr(mul), _ptr(add)), "trace_scale_table")
     return mul, add
 
 
@@ -412,14 +422,10 @@ def witness_wires() -> int:
 def perm_witness(states_t, out=None):
     """Every gate output of the reference's GadgetStrategy (src/strategies/gadget.rs:41-133) for every state:
     [972, n, 4] int64, wire-major in gate order (include/hades252.h).  The input is left untouched."""
-    import torch
     ptr, n, dev = _dev_buffer(states_t, STATE_BYTES, "perm_witness")
-    n_wires = _lib.lib().hades252_witness_wires()
-    wires = torch.empty((n_wires, n, 4), dtype=torch.int64, device=dev) if out is None else out
-    with torch.cuda.device(dev):
-        check(_lib.lib().hades252_perm_witness_dev(ptr, wires.data_ptr(), n, _stream_ptr(dev)), "perm_witness")
+    wires = _dev_empty(dev, witness_wires(), n, 4) if out is None else out
+    _dev_call("perm_witness", dev, "hades252_perm_witness_dev", ptr, wires.data_ptr(), n)
     return wires
-
 
 
 def sponge_blocks(msg_len: int, pad_mode: int = 1) -> int:
@@ -428,6 +434,14 @@ def sponge_blocks(msg_len: int, pad_mode: int = 1) -> int:
     if pad_mode not in (0, 1):
         raise ValueError("sponge_blocks: pad_mode must be 0 or 1")
     return int(_lib.lib().hades252_sponge_blocks(msg_len, pad_mode))
+
+
+def _dev_messages(where: str, msgs_t, msg_len: int):
+    """-> (data_ptr, n, device) of a tensor that holds n messages of msg_len > 0 scalars."""
+    ptr, n_scalars, dev = _dev_buffer(msgs_t, 32, where)
+    if n_scalars % msg_len != 0:
+        raise ValueError("%s: buffer is not a whole number of messages" % where)
+    return ptr, n_scalars // msg_len, dev
 
 
 def sponge_witness(msgs_t, msg_len: int, capacity_mont: int, pad_mode: int = 1, digests: bool = False):
@@ -439,22 +453,15 @@ def sponge_witness(msgs_t, msg_len: int, capacity_mont: int, pad_mode: int = 1, 
     if msg_len < 0:
         raise ValueError("sponge_witness: msg_len must not be negative")
     if msg_len > 0:
-        ptr, n_scalars, dev = _dev_buffer(msgs_t, 32, "sponge_witness")
-        if n_scalars % msg_len != 0:
-            raise ValueError("sponge_witness: buffer is not a whole number of messages")
-        n = n_scalars // msg_len
+        ptr, n, dev = _dev_messages("sponge_witness", msgs_t, msg_len)
     else:
         if not isinstance(msgs_t, torch.Tensor) or msgs_t.device.type != "cuda" or msgs_t.dim() < 1:
             raise TypeError("sponge_witness: msg_len 0 needs a CUDA tensor of shape [n, 0, ...]")
         ptr, n, dev = None, int(msgs_t.shape[0]), msgs_t.device
-    S = sponge_blocks(msg_len, pad_mode)
-    wires = torch.empty((witness_wires(), S, n, 4), dtype=torch.int64, device=dev)
-    inputs = torch.empty((S, n, 5, 4), dtype=torch.int64, device=dev)
-    dig = torch.empty((n, 4), dtype=torch.int64, device=dev) if digests else None
-    with torch.cuda.device(dev):
-        check(_lib.lib().hades252_sponge_witness_dev(ptr, n, msg_len, _tag_arr(capacity_mont), pad_mode, inputs.data_ptr(),
-                                                     wires.data_ptr(), None if dig is None else dig.data_ptr(),
-                                                     _stream_ptr(dev)), "sponge_witness")
+    wires, inputs = _witness_pair(dev, sponge_blocks(msg_len, pad_mode), n)
+    dig = _dev_empty(dev, n, 4) if digests else None
+    _dev_call("sponge_witness", dev, "hades252_sponge_witness_dev", ptr, n, msg_len, _tag_arr(capacity_mont), pad_mode,
+              inputs.data_ptr(), wires.data_ptr(), None if dig is None else dig.data_ptr())
     return (wires, inputs, dig) if digests else (wires, inputs)
 
 
@@ -463,21 +470,14 @@ def merkle_open_witness(leaves_t, tree_t, arity: int, indices_t, tag_mont: int, 
     arity, tag, pad).  Returns (wires [972, depth, n_queries, 4], inputs [depth, n_queries, 5, 4], n_bad): inputs[l, q] =
     [tag, the children of the level-l group on leaf indices[q]'s path, 0 ...]; an index >= n_leaves gets all-zero states
     and is counted in n_bad (synchronises with the device)."""
-    import torch
     ptr, n, dev = _dev_buffer(leaves_t, 32, "merkle_open_witness")
     depth = merkle_depth(n, arity, "merkle_open_witness")
-    tptr, nt, _ = _dev_buffer(tree_t, 32, "merkle_open_witness")
-    if nt != sum(merkle_level_sizes(n, arity)):
-        raise ValueError("merkle_open_witness: tree buffer does not belong to %d leaves" % n)
+    tptr = _tree_of("merkle_open_witness", tree_t, n, arity)
     iptr, nq, _ = _dev_buffer(indices_t, 8, "merkle_open_witness")
-    wires = torch.empty((witness_wires(), depth, nq, 4), dtype=torch.int64, device=dev)
-    inputs = torch.empty((depth, nq, 5, 4), dtype=torch.int64, device=dev)
-    bad = torch.zeros(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        check(_lib.lib().hades252_merkle_open_witness_dev(ptr, tptr, n, arity, _tag_arr(tag_mont),
-                                                          _pad_ptr(pad, depth, "merkle_open_witness"), iptr, nq,
-                                                          inputs.data_ptr(), wires.data_ptr(), bad.data_ptr(),
-                                                          _stream_ptr(dev)), "merkle_open_witness")
+    wires, inputs = _witness_pair(dev, depth, nq)
+    bad = _dev_counter(dev)
+    _dev_call("merkle_open_witness", dev, "hades252_merkle_open_witness_dev", ptr, tptr, n, arity, _tag_arr(tag_mont),
+              _pad_ptr(pad, depth, "merkle_open_witness"), iptr, nq, inputs.data_ptr(), wires.data_ptr(), bad.data_ptr())
     return wires, inputs, int(bad.item())
 
 
@@ -495,23 +495,27 @@ def fr_op(op: int, a_t, b_t=None, impl: int = FR_IMPL_RADIX29):
         if nb != n:
             raise ValueError("fr_op: operand sizes differ")
     out = torch.empty_like(a_t)
-    with torch.cuda.device(dev):
-        check(_lib.lib().hades252_fr_op_dev(op, impl, ptr, bptr, out.data_ptr(), n, _stream_ptr(dev)), "fr_op")
+    _dev_call("fr_op", dev, "hades252_fr_op_dev", op, impl, ptr, bptr, out.data_ptr(), n)
     return out
 
 
 # ---- helpers around the strategy (wire format, Merkle, synthetic data) ----------------------
+def _wire_buffers(where: str, in_t, out_t):
+    """-> (in pointer, out pointer, n, device, out tensor) of a 32-byte-per-scalar conversion; out_t None: a new tensor."""
+    import torch
+    ptr, n, dev = _dev_buffer(in_t, 32, where)
+    out_t = torch.empty_like(in_t) if out_t is None else out_t
+    optr, n2, _ = _dev_buffer(out_t, 32, where)
+    assert n2 == n
+    return ptr, optr, n, dev, out_t
+
+
 def from_bytes(bytes_t, out_t=None):
     """``BlsScalar::from_bytes`` on device: 32-byte canonical LE -> Montgomery limbs.
     Raises ValueError if any input is >= p (the reference returns an error option)."""
-    import torch
-    ptr, n, dev = _dev_buffer(bytes_t, 32, "from_bytes")
-    out_t = torch.empty_like(bytes_t) if out_t is None else out_t
-    optr, n2, _ = _dev_buffer(out_t, 32, "from_bytes")
-    assert n2 == n
-    bad = torch.zeros(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        check(_lib.lib().hades252_from_bytes_dev(ptr, optr, n, bad.data_ptr(), _stream_ptr(dev)), "from_bytes")
+    ptr, optr, n, dev, out_t = _wire_buffers("from_bytes", bytes_t, out_t)
+    bad = _dev_counter(dev)
+    _dev_call("from_bytes", dev, "hades252_from_bytes_dev", ptr, optr, n, bad.data_ptr())
     if int(bad.item()) != 0:
         raise ValueError("from_bytes: %d scalar(s) not canonical (>= p)" % int(bad.item()))
     return out_t
@@ -519,18 +523,9 @@ def from_bytes(bytes_t, out_t=None):
 
 def to_bytes(limbs_t, out_t=None):
     """``BlsScalar::to_bytes`` on device."""
-    import torch
-    ptr, n, dev = _dev_buffer(limbs_t, 32, "to_bytes")
-    out_t = torch.empty_like(limbs_t) if out_t is None else out_t
-    optr, n2, _ = _dev_buffer(out_t, 32, "to_bytes")
-    assert n2 == n
-    with torch.cuda.device(dev):
-        check(_lib.lib().hades252_to_bytes_dev(ptr, optr, n, _stream_ptr(dev)), "to_bytes")
+    ptr, optr, n, dev, out_t = _wire_buffers("to_bytes", limbs_t, out_t)
+    _dev_call("to_bytes", dev, "hades252_to_bytes_dev", ptr, optr, n)
     return out_t
-
-
-def _tag_arr(tag_mont: int):
-    return (ctypes.c_uint64 * 4)(*[(tag_mont >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(4)])
 
 
 def merkle_depth(n: int, arity: int, what: str = "merkle") -> int:
@@ -559,131 +554,114 @@ def _pad_ptr(pad_t, depth: int, what: str):
     return ptr
 
 
+def _tree_of(where: str, tree_t, n: int, arity: int) -> int:
+    """The pointer of ``tree_t`` if it is what ``merkle_build`` returns for n leaves."""
+    tptr, nt, _ = _dev_buffer(tree_t, 32, where)
+    if nt != sum(merkle_level_sizes(n, arity)):
+        raise ValueError("%s: tree buffer does not belong to %d leaves" % (where, n))
+    return tptr
+
+
+def _dev_scratch(dev, scratch, need_bytes: int):
+    """-> (pointer, bytes) of the caller's scratch tensor, or of a new one of need_bytes."""
+    if scratch is None:
+        scratch = _dev_empty(dev, max(need_bytes // 8, 2))
+    return scratch.data_ptr(), scratch.numel() * scratch.element_size()
+
+
 def merkle_level(children_t, arity: int, tag_mont: int, out_idx: int = 1, pad=None):
     """One tree level: parent = perm([tag, c_0 .. c_{arity-1}, 0 ..])[out_idx], arity 1..4.  A ragged level (child
     count not a multiple of the arity) takes ``pad`` (one 32-byte digest on the device; None = zero) for the missing
     children."""
-    import torch
     if arity not in (1, 2, 3, 4):
         raise ValueError("merkle_level: arity must be 1..4")
     ptr, n_children, dev = _dev_buffer(children_t, 32, "merkle_level")
-    n = -(-n_children // arity)
-    parents = torch.empty((n, 4), dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        check(_lib.lib().hades252_merkle_level_pad_dev(ptr, n_children, parents.data_ptr(), arity, _tag_arr(tag_mont),
-                                                       out_idx, _pad_ptr(pad, 1, "merkle_level"), _stream_ptr(dev)),
-              "merkle_level")
+    parents = _dev_empty(dev, -(-n_children // arity), 4)
+    _dev_call("merkle_level", dev, "hades252_merkle_level_pad_dev", ptr, n_children, parents.data_ptr(), arity,
+              _tag_arr(tag_mont), out_idx, _pad_ptr(pad, 1, "merkle_level"))
     return parents
 
 
 def merkle_empty_digests(arity: int, depth: int, e0_mont: int, tag_mont: int, out_idx: int = 1, device="cuda"):
     """The padding table of empty subtrees: [depth, 4] int64 -- pad[0] = e0, pad[l+1] = parent of `arity` x pad[l]."""
-    import torch
-    pad = torch.empty((depth, 4), dtype=torch.int64, device=device)
-    with torch.cuda.device(pad.device):
-        check(_lib.lib().hades252_merkle_empty_digests_dev(arity, depth, _tag_arr(e0_mont), _tag_arr(tag_mont), out_idx,
-                                                           pad.data_ptr(), _stream_ptr(pad.device)), "merkle_empty_digests")
+    pad = _dev_empty(device, depth, 4)
+    _dev_call("merkle_empty_digests", pad.device, "hades252_merkle_empty_digests_dev", arity, depth, _tag_arr(e0_mont),
+              _tag_arr(tag_mont), out_idx, pad.data_ptr())
     return pad
 
 
 def merkle_root(leaves_t, arity: int, tag_mont: int, out_idx: int = 1, scratch=None, pad=None):
     """Root of the arity-`arity` tree over ``leaves_t`` (n_leaves x 32 B; any n_leaves >= 2, arity 2..4)."""
-    import torch
     ptr, n, dev = _dev_buffer(leaves_t, 32, "merkle_root")
     depth = merkle_depth(n, arity, "merkle_root")
-    need = _lib.lib().hades252_merkle_scratch_bytes(n, arity)
-    if scratch is None:
-        scratch = torch.empty(max(need // 8, 2), dtype=torch.int64, device=dev)
-    sptr = scratch.data_ptr()
-    sbytes = scratch.numel() * scratch.element_size()
-    root = torch.empty(4, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        check(_lib.lib().hades252_merkle_root_pad_dev(ptr, n, arity, sptr, sbytes, _tag_arr(tag_mont), out_idx,
-                                                      _pad_ptr(pad, depth, "merkle_root"), root.data_ptr(),
-                                                      _stream_ptr(dev)), "merkle_root")
+    sptr, sbytes = _dev_scratch(dev, scratch, _lib.lib().hades252_merkle_scratch_bytes(n, arity))
+    root = _dev_empty(dev, 4)
+    _dev_call("merkle_root", dev, "hades252_merkle_root_pad_dev", ptr, n, arity, sptr, sbytes, _tag_arr(tag_mont), out_idx,
+              _pad_ptr(pad, depth, "merkle_root"), root.data_ptr())
     return root
 
 
 def merkle_build(leaves_t, arity: int, tag_mont: int, out_idx: int = 1, pad=None):
     """Every level of the tree: [n_1 + n_2 + ... + 1, 4] int64 -- level 1 first, the root last."""
-    import torch
     ptr, n, dev = _dev_buffer(leaves_t, 32, "merkle_build")
     depth = merkle_depth(n, arity, "merkle_build")
-    tree = torch.empty((sum(merkle_level_sizes(n, arity)), 4), dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        check(_lib.lib().hades252_merkle_build_pad_dev(ptr, n, arity, _tag_arr(tag_mont), out_idx,
-                                                       _pad_ptr(pad, depth, "merkle_build"), tree.data_ptr(),
-                                                       _stream_ptr(dev)), "merkle_build")
+    tree = _dev_empty(dev, sum(merkle_level_sizes(n, arity)), 4)
+    _dev_call("merkle_build", dev, "hades252_merkle_build_pad_dev", ptr, n, arity, _tag_arr(tag_mont), out_idx,
+              _pad_ptr(pad, depth, "merkle_build"), tree.data_ptr())
     return tree
 
 
 def merkle_open(leaves_t, tree_t, arity: int, indices_t, pad=None):
     """Authentication paths: [n_queries, depth, arity-1, 4] int64 (siblings in child order, the path node's
     own position (index // arity^l) % arity skipped; positions past the end of a level read pad[l])."""
-    import torch
     ptr, n, dev = _dev_buffer(leaves_t, 32, "merkle_open")
     depth = merkle_depth(n, arity, "merkle_open")
-    tptr, nt, _ = _dev_buffer(tree_t, 32, "merkle_open")
-    if nt != sum(merkle_level_sizes(n, arity)):
-        raise ValueError("merkle_open: tree buffer does not belong to %d leaves" % n)
+    tptr = _tree_of("merkle_open", tree_t, n, arity)
     iptr, nq, _ = _dev_buffer(indices_t, 8, "merkle_open")
     if nq and int(indices_t.max().item()) >= n:
         raise IndexError("merkle_open: leaf index out of range")
-    paths = torch.empty((nq, depth, arity - 1, 4), dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        check(_lib.lib().hades252_merkle_open_pad_dev(ptr, tptr, n, arity, iptr, nq, _pad_ptr(pad, depth, "merkle_open"),
-                                                      paths.data_ptr(), _stream_ptr(dev)), "merkle_open")
+    paths = _dev_empty(dev, nq, depth, arity - 1, 4)
+    _dev_call("merkle_open", dev, "hades252_merkle_open_pad_dev", ptr, tptr, n, arity, iptr, nq,
+              _pad_ptr(pad, depth, "merkle_open"), paths.data_ptr())
     return paths
 
 
 def merkle_verify(leaf_values_t, indices_t, paths_t, arity: int, tag_mont: int, out_idx: int = 1):
     """Roots recomputed from (leaf value, index, opening) per query: [n_queries, 4] int64."""
-    import torch
     lptr, nq, dev = _dev_buffer(leaf_values_t, 32, "merkle_verify")
     iptr, nq2, _ = _dev_buffer(indices_t, 8, "merkle_verify")
     if nq2 != nq or paths_t.shape[0] != nq:
         raise ValueError("merkle_verify: leaves, indices and paths differ in count")
     depth = int(paths_t.shape[1])
     pptr = paths_t.data_ptr() if paths_t.numel() else 0
-    roots = torch.empty((nq, 4), dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        check(_lib.lib().hades252_merkle_verify_dev(lptr, iptr, pptr, nq, depth, arity, _tag_arr(tag_mont), out_idx,
-                                                    roots.data_ptr(), _stream_ptr(dev)), "merkle_verify")
+    roots = _dev_empty(dev, nq, 4)
+    _dev_call("merkle_verify", dev, "hades252_merkle_verify_dev", lptr, iptr, pptr, nq, depth, arity, _tag_arr(tag_mont), out_idx,
+              roots.data_ptr())
     return roots
 
 
 def merkle_update(leaves_t, tree_t, arity: int, indices_t, tag_mont: int, out_idx: int = 1, pad=None):
     """Re-hash, in place in ``tree_t``, the ancestors of the leaves named by ``indices_t`` (device int64/uint64) after the
     caller has overwritten those rows of ``leaves_t``: depth x n_updates permutations instead of the whole tree."""
-    import torch
     ptr, n, dev = _dev_buffer(leaves_t, 32, "merkle_update")
     depth = merkle_depth(n, arity, "merkle_update")
-    tptr, nt, _ = _dev_buffer(tree_t, 32, "merkle_update")
-    if nt != sum(merkle_level_sizes(n, arity)):
-        raise ValueError("merkle_update: tree buffer does not belong to %d leaves" % n)
+    tptr = _tree_of("merkle_update", tree_t, n, arity)
     iptr, nq, _ = _dev_buffer(indices_t, 8, "merkle_update")
-    with torch.cuda.device(dev):
-        check(_lib.lib().hades252_merkle_update_dev(ptr, tptr, n, arity, _tag_arr(tag_mont), out_idx,
-                                                    _pad_ptr(pad, depth, "merkle_update"), iptr, nq, _stream_ptr(dev)),
-              "merkle_update")
+    _dev_call("merkle_update", dev, "hades252_merkle_update_dev", ptr, tptr, n, arity, _tag_arr(tag_mont), out_idx,
+              _pad_ptr(pad, depth, "merkle_update"), iptr, nq)
     return tree_t
 
 
 def merkle_forest(leaves_t, n_trees: int, arity: int, tag_mont: int, out_idx: int = 1, scratch=None):
     """Roots of n_trees equal trees (leaves contiguous, tree after tree; leaves per tree a power of the arity)."""
-    import torch
     ptr, n, dev = _dev_buffer(leaves_t, 32, "merkle_forest")
     if n_trees <= 0 or n % n_trees:
         raise ValueError("merkle_forest: %d leaves do not split into %d trees" % (n, n_trees))
     per = n // n_trees
-    need = _lib.lib().hades252_merkle_forest_scratch_bytes(n_trees, per, arity)
-    if scratch is None:
-        scratch = torch.empty(max(need // 8, 2), dtype=torch.int64, device=dev)
-    roots = torch.empty((n_trees, 4), dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        check(_lib.lib().hades252_merkle_forest_dev(ptr, n_trees, per, arity, scratch.data_ptr(),
-                                                    scratch.numel() * scratch.element_size(), _tag_arr(tag_mont), out_idx,
-                                                    roots.data_ptr(), _stream_ptr(dev)), "merkle_forest")
+    sptr, sbytes = _dev_scratch(dev, scratch, _lib.lib().hades252_merkle_forest_scratch_bytes(n_trees, per, arity))
+    roots = _dev_empty(dev, n_trees, 4)
+    _dev_call("merkle_forest", dev, "hades252_merkle_forest_dev", ptr, n_trees, per, arity, sptr, sbytes, _tag_arr(tag_mont),
+              out_idx, roots.data_ptr())
     return roots
 
 
@@ -699,18 +677,11 @@ def merkle4_root(leaves_t, tag_mont: int, out_idx: int = 1, scratch=None):
 def sponge_hash(msgs_t, msg_len: int, capacity_mont: int, pad_mode: int = 1):
     """Batched fixed-length sponge (include/hades252.h): msgs_t holds n messages of msg_len
     scalars; returns [n, 4] int64 digests (word 1 of the final state)."""
-    import torch
-    if msg_len > 0:
-        ptr, n_scalars, dev = _dev_buffer(msgs_t, 32, "sponge_hash")
-        if n_scalars % msg_len != 0:
-            raise ValueError("sponge_hash: buffer is not a whole number of messages")
-        n = n_scalars // msg_len
-    else:
+    if msg_len <= 0:
         raise ValueError("sponge_hash: msg_len must be positive for a tensor batch")
-    out = torch.empty((n, 4), dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        check(_lib.lib().hades252_sponge_hash_dev(ptr, n, msg_len, _tag_arr(capacity_mont), pad_mode,
-                                                  out.data_ptr(), _stream_ptr(dev)), "sponge_hash")
+    ptr, n, dev = _dev_messages("sponge_hash", msgs_t, msg_len)
+    out = _dev_empty(dev, n, 4)
+    _dev_call("sponge_hash", dev, "hades252_sponge_hash_dev", ptr, n, msg_len, _tag_arr(capacity_mont), pad_mode, out.data_ptr())
     return out
 
 
@@ -719,23 +690,19 @@ def sponge_hash_var(scalars_t, offsets_t, lengths_t, capacity_mont: int, pad_mod
     (offsets / lengths: int64 CUDA tensors, in scalars).  Returns [n, 4] int64 digests.  ``sort``: order the messages
     by block count on the device first (ragged batches: the 64 messages of a wave then need the same number of
     permutations); same digests."""
-    import torch
     sptr, n_scalars, dev = _dev_buffer(scalars_t, 32, "sponge_hash_var")
     optr, n, _ = _dev_buffer(offsets_t, 8, "sponge_hash_var")
     lptr, n2, _ = _dev_buffer(lengths_t, 8, "sponge_hash_var")
     if n != n2:
         raise ValueError("sponge_hash_var: offsets and lengths differ in size")
-    out = torch.empty((n, 4), dtype=torch.int64, device=dev)
-    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    out = _dev_empty(dev, n, 4)
+    bad = _dev_counter(dev)
     scratch, sbytes = None, 0
     if sort:
         sbytes = _lib.lib().hades252_sponge_sort_scratch_bytes(n)
-        scratch = torch.empty((sbytes + 15) // 16 * 2, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        check(_lib.lib().hades252_sponge_hash_var_ex_dev(sptr, n_scalars, optr, lptr, n, _tag_arr(capacity_mont), pad_mode,
-                                                         out.data_ptr(), bad.data_ptr(),
-                                                         scratch.data_ptr() if sort else 0, sbytes, _stream_ptr(dev)),
-              "sponge_hash_var")
+        scratch = _dev_empty(dev, (sbytes + 15) // 16 * 2)
+    _dev_call("sponge_hash_var", dev, "hades252_sponge_hash_var_ex_dev", sptr, n_scalars, optr, lptr, n, _tag_arr(capacity_mont),
+              pad_mode, out.data_ptr(), bad.data_ptr(), scratch.data_ptr() if sort else 0, sbytes)
     if int(bad.item()) != 0:
         raise IndexError("sponge_hash_var: %d message(s) reach outside the scalar pool" % int(bad.item()))
     return out
@@ -746,35 +713,32 @@ SPONGE_PRESETS = {"sponge/pad10": {"capacity": 1 << 64, "pad_mode": 1, "digest_w
                   "merkle/arity4": {"tag": 15, "arity": 4, "digest_word": 1}}
 
 
+def _resident_states(where: str, n: int, word0_mont: int, device):
+    """n sponge states [n, 5, 4] on ``device``, word 0 set (``hades252_sponge_init_dev``)."""
+    states = _dev_empty(device, n, WIDTH, 4)
+    _dev_call(where, states.device, "hades252_sponge_init_dev", states.data_ptr(), n, _tag_arr(word0_mont))
+    return states
+
+
 class SpongeStates:
     """Streaming sponge (``hades252_sponge_init_dev`` / ``_absorb_dev`` / ``_squeeze_dev``): n states resident on the
     device; absorb blocks of 4 scalars whenever they arrive, squeeze when done."""
 
     def __init__(self, n: int, capacity_mont: int, device="cuda"):
-        import torch
-        self.states = torch.empty((n, WIDTH, 4), dtype=torch.int64, device=device)
-        with torch.cuda.device(self.states.device):
-            check(_lib.lib().hades252_sponge_init_dev(self.states.data_ptr(), n, _tag_arr(capacity_mont),
-                                                      _stream_ptr(self.states.device)), "sponge_init")
+        self.states = _resident_states("sponge_init", n, capacity_mont, device)
 
     def absorb(self, blocks_t) -> None:
         """blocks_t: [n, blocks_each, 4 scalars] (any shape with n * blocks_each * 128 bytes, state-major)."""
-        import torch
         n = self.states.shape[0]
         ptr, n_blocks, dev = _dev_buffer(blocks_t, 128, "sponge_absorb")
         if n == 0 or n_blocks % n:
             raise ValueError("sponge_absorb: %d blocks do not split evenly over %d states" % (n_blocks, n))
-        with torch.cuda.device(dev):
-            check(_lib.lib().hades252_sponge_absorb_dev(self.states.data_ptr(), ptr, n, n_blocks // n, _stream_ptr(dev)),
-                  "sponge_absorb")
+        _dev_call("sponge_absorb", dev, "hades252_sponge_absorb_dev", self.states.data_ptr(), ptr, n, n_blocks // n)
 
     def squeeze(self, word: int = 1):
-        import torch
         n, dev = self.states.shape[0], self.states.device
-        out = torch.empty((n, 4), dtype=torch.int64, device=dev)
-        with torch.cuda.device(dev):
-            check(_lib.lib().hades252_sponge_squeeze_dev(self.states.data_ptr(), out.data_ptr(), n, word, _stream_ptr(dev)),
-                  "sponge_squeeze")
+        out = _dev_empty(dev, n, 4)
+        _dev_call("sponge_squeeze", dev, "hades252_sponge_squeeze_dev", self.states.data_ptr(), out.data_ptr(), n, word)
         return out
 
 
@@ -790,30 +754,40 @@ def _same_device(what: str, dev, *others) -> None:
             raise ValueError("%s: every tensor must be on %s (got one on %s)" % (what, dev, d))
 
 
-def _cipher_shapes(what: str, msg_len: int, keys_units: int, nonces_units: int) -> int:
+def _cipher_shapes(what: str, msg_len: int, decrypt: bool, words_units: int, keys_units: int, nonces_units: int) -> int:
+    """The shape rules of the cipher, host and device: -> n messages.  The words are n messages of msg_len scalars
+    (encrypt) or n ciphers of msg_len + 1 (decrypt)."""
     if not 1 <= msg_len <= _lib.CIPHER_MAX_LEN:
         raise ValueError("%s: msg_len must be in 1 .. %d (got %d)" % (what, _lib.CIPHER_MAX_LEN, msg_len))
     if keys_units != 2 * nonces_units:
         raise ValueError("%s: %d key scalars for %d nonces (two per message)" % (what, keys_units, nonces_units))
+    each = msg_len + 1 if decrypt else msg_len
+    if words_units != nonces_units * each:
+        raise ValueError("%s: buffer is not %d %s of %d scalars" % (what, nonces_units, "ciphers" if decrypt else "messages", each))
     return nonces_units
+
+
+def _cipher_front(what: str, words_t, keys_t, nonces_t, msg_len: int, decrypt: bool):
+    """The arguments the four device calls of the cipher share: -> ((words, keys, nonces) pointers, n, device)."""
+    kptr, n_keys, dev = _dev_buffer(keys_t, 32, what)
+    nptr, n_nonces, ndev = _dev_buffer(nonces_t, 32, what)
+    wptr, n_words, wdev = _dev_buffer(words_t, 32, what)
+    _same_device(what, dev, ndev, wdev)
+    return (wptr, kptr, nptr), _cipher_shapes(what, msg_len, decrypt, n_words, n_keys, n_nonces), dev
+
+
+def _decrypt_outputs(dev, n: int, msg_len: int):
+    """(msgs [n, msg_len, 4], ok [n] uint8, rejected counter) of a decryption."""
+    return _dev_empty(dev, n, msg_len, 4), _dev_empty(dev, n, dtype="uint8"), _dev_counter(dev)
 
 
 def cipher_encrypt(msgs_t, keys_t, nonces_t, msg_len: int, domain_mont: int = CIPHER_DOMAIN):
     """Batched Poseidon cipher, encrypt (``hades252_cipher_encrypt_dev``): msgs_t holds n messages of msg_len scalars,
     keys_t n x 2 scalars, nonces_t n scalars (CUDA tensors, Montgomery limbs).  Returns [n, msg_len + 1, 4] int64: the
     cipher words, the tag last."""
-    import torch
-    kptr, n_keys, dev = _dev_buffer(keys_t, 32, "cipher_encrypt")
-    nptr, n_nonces, ndev = _dev_buffer(nonces_t, 32, "cipher_encrypt")
-    mptr, n_words, mdev = _dev_buffer(msgs_t, 32, "cipher_encrypt")
-    _same_device("cipher_encrypt", dev, ndev, mdev)
-    n = _cipher_shapes("cipher_encrypt", msg_len, n_keys, n_nonces)
-    if n_words != n * msg_len:
-        raise ValueError("cipher_encrypt: buffer is not %d messages of %d scalars" % (n, msg_len))
-    out = torch.empty((n, msg_len + 1, 4), dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        check(_lib.lib().hades252_cipher_encrypt_dev(mptr, kptr, nptr, n, msg_len, _tag_arr(domain_mont), out.data_ptr(),
-                                                     _stream_ptr(dev)), "cipher_encrypt")
+    ptrs, n, dev = _cipher_front("cipher_encrypt", msgs_t, keys_t, nonces_t, msg_len, False)
+    out = _dev_empty(dev, n, msg_len + 1, 4)
+    _dev_call("cipher_encrypt", dev, "hades252_cipher_encrypt_dev", *ptrs, n, msg_len, _tag_arr(domain_mont), out.data_ptr())
     return out
 
 
@@ -821,20 +795,10 @@ def cipher_decrypt(ciphers_t, keys_t, nonces_t, msg_len: int, domain_mont: int =
     """Batched Poseidon cipher, decrypt (``hades252_cipher_decrypt_dev``): ciphers_t holds n x (msg_len + 1) scalars.
     Returns (msgs [n, msg_len, 4] int64, ok [n] uint8, n_rejected); a rejected message (wrong tag, or a cipher word that
     is not canonical) comes out as zeros.  n_rejected synchronises with the device."""
-    import torch
-    kptr, n_keys, dev = _dev_buffer(keys_t, 32, "cipher_decrypt")
-    nptr, n_nonces, ndev = _dev_buffer(nonces_t, 32, "cipher_decrypt")
-    cptr, n_words, cdev = _dev_buffer(ciphers_t, 32, "cipher_decrypt")
-    _same_device("cipher_decrypt", dev, ndev, cdev)
-    n = _cipher_shapes("cipher_decrypt", msg_len, n_keys, n_nonces)
-    if n_words != n * (msg_len + 1):
-        raise ValueError("cipher_decrypt: buffer is not %d ciphers of %d scalars" % (n, msg_len + 1))
-    out = torch.empty((n, msg_len, 4), dtype=torch.int64, device=dev)
-    ok = torch.empty(n, dtype=torch.uint8, device=dev)
-    rej = torch.zeros(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        check(_lib.lib().hades252_cipher_decrypt_dev(cptr, kptr, nptr, n, msg_len, _tag_arr(domain_mont), out.data_ptr(),
-                                                     ok.data_ptr(), rej.data_ptr(), _stream_ptr(dev)), "cipher_decrypt")
+    ptrs, n, dev = _cipher_front("cipher_decrypt", ciphers_t, keys_t, nonces_t, msg_len, True)
+    out, ok, rej = _decrypt_outputs(dev, n, msg_len)
+    _dev_call("cipher_decrypt", dev, "hades252_cipher_decrypt_dev", *ptrs, n, msg_len, _tag_arr(domain_mont), out.data_ptr(),
+              ok.data_ptr(), rej.data_ptr())
     return out, ok, int(rej.item())
 
 
@@ -845,31 +809,16 @@ def cipher_perms(msg_len: int) -> int:
     return int(_lib.lib().hades252_cipher_perms(msg_len))
 
 
-def _cipher_witness_buffers(torch, dev, n: int, msg_len: int):
-    S = cipher_perms(msg_len)
-    return (torch.empty((witness_wires(), S, n, 4), dtype=torch.int64, device=dev),
-            torch.empty((S, n, 5, 4), dtype=torch.int64, device=dev))
-
-
 def cipher_encrypt_witness(msgs_t, keys_t, nonces_t, msg_len: int, domain_mont: int = CIPHER_DOMAIN):
     """Gadget witness of the cipher, encrypt (``hades252_cipher_encrypt_witness_dev``; the arguments of ``cipher_encrypt``).
     Returns (wires [972, S, n, 4], inputs [S, n, 5, 4], ciphers [n, msg_len + 1, 4]) with S = cipher_perms(msg_len):
     inputs[s, i] enters permutation s of message i, wires.reshape(972, S * n, 4) == perm_witness(inputs) byte for byte,
     and the ciphers are those of ``cipher_encrypt``."""
-    import torch
-    kptr, n_keys, dev = _dev_buffer(keys_t, 32, "cipher_encrypt_witness")
-    nptr, n_nonces, ndev = _dev_buffer(nonces_t, 32, "cipher_encrypt_witness")
-    mptr, n_words, mdev = _dev_buffer(msgs_t, 32, "cipher_encrypt_witness")
-    _same_device("cipher_encrypt_witness", dev, ndev, mdev)
-    n = _cipher_shapes("cipher_encrypt_witness", msg_len, n_keys, n_nonces)
-    if n_words != n * msg_len:
-        raise ValueError("cipher_encrypt_witness: buffer is not %d messages of %d scalars" % (n, msg_len))
-    wires, inputs = _cipher_witness_buffers(torch, dev, n, msg_len)
-    out = torch.empty((n, msg_len + 1, 4), dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        check(_lib.lib().hades252_cipher_encrypt_witness_dev(mptr, kptr, nptr, n, msg_len, _tag_arr(domain_mont),
-                                                             inputs.data_ptr(), wires.data_ptr(), out.data_ptr(),
-                                                             _stream_ptr(dev)), "cipher_encrypt_witness")
+    ptrs, n, dev = _cipher_front("cipher_encrypt_witness", msgs_t, keys_t, nonces_t, msg_len, False)
+    wires, inputs = _witness_pair(dev, cipher_perms(msg_len), n)
+    out = _dev_empty(dev, n, msg_len + 1, 4)
+    _dev_call("cipher_encrypt_witness", dev, "hades252_cipher_encrypt_witness_dev", *ptrs, n, msg_len, _tag_arr(domain_mont),
+              inputs.data_ptr(), wires.data_ptr(), out.data_ptr())
     return wires, inputs, out
 
 
@@ -878,45 +827,22 @@ def cipher_decrypt_witness(ciphers_t, keys_t, nonces_t, msg_len: int, domain_mon
     Returns (wires [972, S, n, 4], inputs [S, n, 5, 4], msgs [n, msg_len, 4], ok [n] uint8, n_rejected): the inputs carry
     the cipher words reduced mod p, so they are canonical for every message; msgs, ok and n_rejected are those of
     ``cipher_decrypt``.  n_rejected synchronises with the device."""
-    import torch
-    kptr, n_keys, dev = _dev_buffer(keys_t, 32, "cipher_decrypt_witness")
-    nptr, n_nonces, ndev = _dev_buffer(nonces_t, 32, "cipher_decrypt_witness")
-    cptr, n_words, cdev = _dev_buffer(ciphers_t, 32, "cipher_decrypt_witness")
-    _same_device("cipher_decrypt_witness", dev, ndev, cdev)
-    n = _cipher_shapes("cipher_decrypt_witness", msg_len, n_keys, n_nonces)
-    if n_words != n * (msg_len + 1):
-        raise ValueError("cipher_decrypt_witness: buffer is not %d ciphers of %d scalars" % (n, msg_len + 1))
-    wires, inputs = _cipher_witness_buffers(torch, dev, n, msg_len)
-    out = torch.empty((n, msg_len, 4), dtype=torch.int64, device=dev)
-    ok = torch.empty(n, dtype=torch.uint8, device=dev)
-    rej = torch.zeros(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        check(_lib.lib().hades252_cipher_decrypt_witness_dev(cptr, kptr, nptr, n, msg_len, _tag_arr(domain_mont),
-                                                             inputs.data_ptr(), wires.data_ptr(), out.data_ptr(),
-                                                             ok.data_ptr(), rej.data_ptr(), _stream_ptr(dev)),
-              "cipher_decrypt_witness")
+    ptrs, n, dev = _cipher_front("cipher_decrypt_witness", ciphers_t, keys_t, nonces_t, msg_len, True)
+    wires, inputs = _witness_pair(dev, cipher_perms(msg_len), n)
+    out, ok, rej = _decrypt_outputs(dev, n, msg_len)
+    _dev_call("cipher_decrypt_witness", dev, "hades252_cipher_decrypt_witness_dev", *ptrs, n, msg_len, _tag_arr(domain_mont),
+              inputs.data_ptr(), wires.data_ptr(), out.data_ptr(), ok.data_ptr(), rej.data_ptr())
     return wires, inputs, out, ok, int(rej.item())
 
 
-def _host_scalars(a, what: str) -> int:
-    a = _host_u64(a, what)
-    if a.size % 4:
-        raise ValueError("%s: %d limbs is not a whole number of scalars" % (what, a.size))
-    return a.size // 4
-
-
-def _ptr(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
+def _cipher_host_front(what: str, words, keys, nonces, msg_len: int, decrypt: bool) -> int:
+    return _cipher_shapes(what, msg_len, decrypt, *[_host_units(a, what) for a in (words, keys, nonces)])
 
 
 def cipher_encrypt_host(msgs: np.ndarray, keys: np.ndarray, nonces: np.ndarray, msg_len: int,
                         domain_mont: int = CIPHER_DOMAIN) -> np.ndarray:
     """``hades252_cipher_encrypt`` on HOST arrays (C-contiguous uint64, Montgomery limbs): -> [n, msg_len + 1, 4] uint64."""
-    n_words = _host_scalars(msgs, "cipher_encrypt_host")
-    n = _cipher_shapes("cipher_encrypt_host", msg_len, _host_scalars(keys, "cipher_encrypt_host"),
-                       _host_scalars(nonces, "cipher_encrypt_host"))
-    if n_words != n * msg_len:
-        raise ValueError("cipher_encrypt_host: buffer is not %d messages of %d scalars" % (n, msg_len))
+    n = _cipher_host_front("cipher_encrypt_host", msgs, keys, nonces, msg_len, False)
     out = np.zeros((n, msg_len + 1, 4), dtype=np.uint64)
     check(_lib.lib().hades252_cipher_encrypt(_ptr(msgs), _ptr(keys), _ptr(nonces), n, msg_len, _tag_arr(domain_mont),
                                              _ptr(out)), "cipher_encrypt_host")
@@ -926,11 +852,7 @@ def cipher_encrypt_host(msgs: np.ndarray, keys: np.ndarray, nonces: np.ndarray, 
 def cipher_decrypt_host(ciphers: np.ndarray, keys: np.ndarray, nonces: np.ndarray, msg_len: int,
                         domain_mont: int = CIPHER_DOMAIN):
     """``hades252_cipher_decrypt`` on HOST arrays: -> (msgs [n, msg_len, 4] uint64, ok [n] uint8, n_rejected)."""
-    n_words = _host_scalars(ciphers, "cipher_decrypt_host")
-    n = _cipher_shapes("cipher_decrypt_host", msg_len, _host_scalars(keys, "cipher_decrypt_host"),
-                       _host_scalars(nonces, "cipher_decrypt_host"))
-    if n_words != n * (msg_len + 1):
-        raise ValueError("cipher_decrypt_host: buffer is not %d ciphers of %d scalars" % (n, msg_len + 1))
+    n = _cipher_host_front("cipher_decrypt_host", ciphers, keys, nonces, msg_len, True)
     out = np.zeros((n, msg_len, 4), dtype=np.uint64)
     ok = np.zeros(n, dtype=np.uint8)
     rej = ctypes.c_size_t(0)
@@ -965,46 +887,56 @@ def safe_pattern(calls):
     return int(n_in.value), int(n_out.value), int(n_perms.value)
 
 
+def _aggregate(pattern):
+    """A valid pattern with neighbouring calls of one kind merged: [[kind, words], ...]."""
+    calls = []
+    for kind, n in pattern:
+        if calls and calls[-1][0] == kind:
+            calls[-1][1] += n
+        else:
+            calls.append([kind, n])
+    return calls
+
+
 def safe_tag_input(pattern, domain_sep: int) -> bytes:
     """The bytes SAFE hashes into a tag: the aggregated calls as big-endian 32-bit words, then the 64-bit domain separator
     big-endian.  NAMED, NOT PINNED (like SPONGE_PRESETS); hashing them to a scalar stays the caller's."""
     safe_pattern(pattern)
-    words = []
-    for kind, n in pattern:
-        if words and (words[-1] & _lib.SAFE_ABSORB) == _SAFE_KINDS[kind]:
-            words[-1] += n
-        else:
-            words.append(_SAFE_KINDS[kind] | n)
-    return b"".join(w.to_bytes(4, "big") for w in words) + int(domain_sep).to_bytes(8, "big")
+    return b"".join((_SAFE_KINDS[kind] | n).to_bytes(4, "big") for kind, n in _aggregate(pattern)) + \
+        int(domain_sep).to_bytes(8, "big")
+
+
+def _safe_front(what: str, pattern):
+    """What the three whole-pattern calls share: -> (the pattern as the library takes it (array, count), words absorbed,
+    words squeezed, permutations), each per sponge."""
+    n_in, n_out, n_perms = safe_pattern(pattern)
+    return _safe_calls(pattern, what), n_in, n_out, n_perms
+
+
+def _whole_inputs(what: str, n_words: int, n_in: int) -> int:
+    """How many sponges n_words scalars feed, n_in each."""
+    if n_words % n_in:
+        raise ValueError("%s: %d scalars are not a whole number of inputs of %d" % (what, n_words, n_in))
+    return n_words // n_in
 
 
 def safe_hash(inputs_t, pattern, tag_mont: int):
     """Batched duplex sponge, the whole pattern in one launch (``hades252_safe_hash_dev``): inputs_t holds n x n_in scalars
     (CUDA tensor, Montgomery limbs, message-major, in call order).  Returns [n, n_out, 4] int64."""
-    import torch
-    n_in, n_out, _ = safe_pattern(pattern)
-    arr, k = _safe_calls(pattern, "safe_hash")
+    calls, n_in, n_out, _ = _safe_front("safe_hash", pattern)
     ptr, n_words, dev = _dev_buffer(inputs_t, 32, "safe_hash")
-    if n_words % n_in:
-        raise ValueError("safe_hash: %d scalars are not a whole number of inputs of %d" % (n_words, n_in))
-    n = n_words // n_in
-    out = torch.empty((n, n_out, 4), dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        check(_lib.lib().hades252_safe_hash_dev(ptr, n, arr, k, _tag_arr(tag_mont), out.data_ptr(), _stream_ptr(dev)),
-              "safe_hash")
+    n = _whole_inputs("safe_hash", n_words, n_in)
+    out = _dev_empty(dev, n, n_out, 4)
+    _dev_call("safe_hash", dev, "hades252_safe_hash_dev", ptr, n, *calls, _tag_arr(tag_mont), out.data_ptr())
     return out
 
 
 def safe_hash_host(inputs: np.ndarray, pattern, tag_mont: int) -> np.ndarray:
     """``hades252_safe_hash`` on a HOST array (C-contiguous uint64, Montgomery limbs): -> [n, n_out, 4] uint64."""
-    n_in, n_out, _ = safe_pattern(pattern)
-    arr, k = _safe_calls(pattern, "safe_hash_host")
-    n_words = _host_scalars(inputs, "safe_hash_host")
-    if n_words % n_in:
-        raise ValueError("safe_hash_host: %d scalars are not a whole number of inputs of %d" % (n_words, n_in))
-    n = n_words // n_in
+    calls, n_in, n_out, _ = _safe_front("safe_hash_host", pattern)
+    n = _whole_inputs("safe_hash_host", _host_units(inputs, "safe_hash_host"), n_in)
     out = np.zeros((n, n_out, 4), dtype=np.uint64)
-    check(_lib.lib().hades252_safe_hash(_ptr(inputs), n, arr, k, _tag_arr(tag_mont), _ptr(out)), "safe_hash_host")
+    check(_lib.lib().hades252_safe_hash(_ptr(inputs), n, *calls, _tag_arr(tag_mont), _ptr(out)), "safe_hash_host")
     return out
 
 
@@ -1013,21 +945,13 @@ class SafeSponge:
     ``_squeeze_dev``), for callers whose next input depends on what they read.  Calls may be split (absorb(2) then
     absorb(1) serves ("absorb", 3)); a call of the wrong kind, one that overruns the pattern's current call, or ``finish``
     before the pattern is used up raises ValueError: the analogue of dusk-safe's IO-pattern violation."""
+    _NAME = "SafeSponge"
 
     def __init__(self, n: int, pattern, tag_mont: int, device="cuda"):
-        import torch
         safe_pattern(pattern)
-        self._todo = []                                   # aggregated calls still to serve: [kind, words left]
-        for kind, k in pattern:
-            if self._todo and self._todo[-1][0] == kind:
-                self._todo[-1][1] += k
-            else:
-                self._todo.append([kind, k])
+        self._todo = _aggregate(pattern)                  # aggregated calls still to serve: [kind, words left]
         self._cursor = ctypes.c_uint32(0)
-        self.states = torch.empty((n, WIDTH, 4), dtype=torch.int64, device=device)
-        with torch.cuda.device(self.states.device):
-            check(_lib.lib().hades252_sponge_init_dev(self.states.data_ptr(), n, _tag_arr(tag_mont),
-                                                      _stream_ptr(self.states.device)), "SafeSponge")
+        self.states = _resident_states("SafeSponge", n, tag_mont, device)
 
     def _take(self, kind: str, k: int) -> None:
         if k <= 0:
@@ -1044,31 +968,32 @@ class SafeSponge:
         if self._todo[0][1] == 0:
             self._todo.pop(0)
 
+    def _run(self, kind: str, k: int, *args) -> None:
+        """The library call that serves k words of the current call (``_take`` has agreed to them; ``args``: what the
+        library takes between the sponge count and the pattern cursor), then ticks them off."""
+        self._lib_call(kind, self.states.data_ptr(), self.states.shape[0], *args, ctypes.byref(self._cursor))
+        self._took(k)
+
+    def _lib_call(self, kind: str, *args) -> None:
+        _dev_call("%s.%s" % (self._NAME, kind), self.states.device, "hades252_safe_%s_dev" % kind, *args)
+
     def absorb(self, t) -> None:
         """t: n x k scalars (state-major) for the next k words of the current absorb call."""
-        import torch
+        where = self._NAME + ".absorb"
         n = self.states.shape[0]
-        ptr, n_words, dev = _dev_buffer(t, 32, "SafeSponge.absorb")
-        _same_device("SafeSponge.absorb", self.states.device, dev)
+        ptr, n_words, dev = _dev_buffer(t, 32, where)
+        _same_device(where, self.states.device, dev)
         if n == 0 or n_words % n:
-            raise ValueError("SafeSponge.absorb: %d scalars do not split evenly over %d sponges" % (n_words, n))
+            raise ValueError("%s: %d scalars do not split evenly over %d sponges" % (where, n_words, n))
         k = n_words // n
         self._take("absorb", k)
-        with torch.cuda.device(dev):
-            check(_lib.lib().hades252_safe_absorb_dev(self.states.data_ptr(), n, ptr, k, ctypes.byref(self._cursor),
-                                                      _stream_ptr(dev)), "SafeSponge.absorb")
-        self._took(k)
+        self._run("absorb", k, ptr, k)
 
     def squeeze(self, k: int):
         """-> [n, k, 4] int64: the next k words of the current squeeze call."""
-        import torch
-        n, dev = self.states.shape[0], self.states.device
         self._take("squeeze", k)
-        out = torch.empty((n, k, 4), dtype=torch.int64, device=dev)
-        with torch.cuda.device(dev):
-            check(_lib.lib().hades252_safe_squeeze_dev(self.states.data_ptr(), n, k, out.data_ptr(),
-                                                       ctypes.byref(self._cursor), _stream_ptr(dev)), "SafeSponge.squeeze")
-        self._took(k)
+        out = _dev_empty(self.states.device, self.states.shape[0], k, 4)
+        self._run("squeeze", k, k, out.data_ptr())
         return out
 
     def finish(self) -> None:
@@ -1082,19 +1007,13 @@ def safe_witness(inputs_t, pattern, tag_mont: int):
     ``safe_hash``).  Returns (wires [972, S, n, 4], inputs [S, n, 5, 4], out [n, n_out, 4]) with S the pattern's
     permutations per sponge: inputs[s, i] enters permutation s of sponge i, wires.reshape(972, S * n, 4) ==
     perm_witness(inputs) byte for byte, and out is what ``safe_hash`` returns."""
-    import torch
-    n_in, n_out, S = safe_pattern(pattern)
-    arr, k = _safe_calls(pattern, "safe_witness")
+    calls, n_in, n_out, S = _safe_front("safe_witness", pattern)
     ptr, n_words, dev = _dev_buffer(inputs_t, 32, "safe_witness")
-    if n_words % n_in:
-        raise ValueError("safe_witness: %d scalars are not a whole number of inputs of %d" % (n_words, n_in))
-    n = n_words // n_in
-    wires = torch.empty((witness_wires(), S, n, 4), dtype=torch.int64, device=dev)
-    inputs = torch.empty((S, n, 5, 4), dtype=torch.int64, device=dev)
-    out = torch.empty((n, n_out, 4), dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        check(_lib.lib().hades252_safe_witness_dev(ptr, n, arr, k, _tag_arr(tag_mont), inputs.data_ptr(), wires.data_ptr(),
-                                                   out.data_ptr(), _stream_ptr(dev)), "safe_witness")
+    n = _whole_inputs("safe_witness", n_words, n_in)
+    wires, inputs = _witness_pair(dev, S, n)
+    out = _dev_empty(dev, n, n_out, 4)
+    _dev_call("safe_witness", dev, "hades252_safe_witness_dev", ptr, n, *calls, _tag_arr(tag_mont), inputs.data_ptr(),
+              wires.data_ptr(), out.data_ptr())
     return wires, inputs, out
 
 
@@ -1103,47 +1022,18 @@ class SafeWitnessSponge(SafeSponge):
     ``_squeeze_witness_dev``): it owns the two record buffers, sized for the pattern's S permutations per sponge, and the
     step counter.  After ``finish`` (which also demands that all S steps were recorded) ``wires`` [972, S, n, 4] and
     ``inputs`` [S, n, 5, 4] hold what ``safe_witness`` returns for the same words."""
+    _NAME = "SafeWitnessSponge"
 
     def __init__(self, n: int, pattern, tag_mont: int, device="cuda"):
-        import torch
         super().__init__(n, pattern, tag_mont, device)
         self._steps = safe_pattern(pattern)[2]
         self._step = ctypes.c_size_t(0)
-        dev = self.states.device
-        self._wires = torch.empty((witness_wires(), self._steps, n, 4), dtype=torch.int64, device=dev)
-        self._inputs = torch.empty((self._steps, n, 5, 4), dtype=torch.int64, device=dev)
+        self._wires, self._inputs = _witness_pair(self.states.device, self._steps, n)
         self._finished = False
 
-    def absorb(self, t) -> None:
-        """t: n x k scalars (state-major) for the next k words of the current absorb call."""
-        import torch
-        n = self.states.shape[0]
-        ptr, n_words, dev = _dev_buffer(t, 32, "SafeWitnessSponge.absorb")
-        _same_device("SafeWitnessSponge.absorb", self.states.device, dev)
-        if n == 0 or n_words % n:
-            raise ValueError("SafeWitnessSponge.absorb: %d scalars do not split evenly over %d sponges" % (n_words, n))
-        k = n_words // n
-        self._take("absorb", k)
-        with torch.cuda.device(dev):
-            check(_lib.lib().hades252_safe_absorb_witness_dev(self.states.data_ptr(), n, ptr, k, ctypes.byref(self._cursor),
-                                                              self._inputs.data_ptr(), self._wires.data_ptr(), self._steps,
-                                                              ctypes.byref(self._step), _stream_ptr(dev)),
-                  "SafeWitnessSponge.absorb")
-        self._took(k)
-
-    def squeeze(self, k: int):
-        """-> [n, k, 4] int64: the next k words of the current squeeze call."""
-        import torch
-        n, dev = self.states.shape[0], self.states.device
-        self._take("squeeze", k)
-        out = torch.empty((n, k, 4), dtype=torch.int64, device=dev)
-        with torch.cuda.device(dev):
-            check(_lib.lib().hades252_safe_squeeze_witness_dev(self.states.data_ptr(), n, k, out.data_ptr(),
-                                                               ctypes.byref(self._cursor), self._inputs.data_ptr(),
-                                                               self._wires.data_ptr(), self._steps, ctypes.byref(self._step),
-                                                               _stream_ptr(dev)), "SafeWitnessSponge.squeeze")
-        self._took(k)
-        return out
+    def _lib_call(self, kind: str, *args) -> None:
+        _dev_call("%s.%s" % (self._NAME, kind), self.states.device, "hades252_safe_%s_witness_dev" % kind, *args,
+                  self._inputs.data_ptr(), self._wires.data_ptr(), self._steps, ctypes.byref(self._step))
 
     def finish(self) -> None:
         """The pattern must be used up; ``wires`` and ``inputs`` are readable afterwards."""
@@ -1179,10 +1069,7 @@ def grind(seeds: np.ndarray, word: int, out_idx: int, target: int, first_nonce: 
     x in [first_nonce, first_nonce + max_nonces) for which word ``out_idx`` of perm(seed with seed[word] + x) is, as a
     canonical integer, strictly below ``target`` (a Python int below 2^256).  -> (nonces uint64 [n], found bool [n]);
     nonces[j] is 0 where found[j] is False."""
-    if not isinstance(seeds, np.ndarray) or seeds.dtype != np.uint64 or not seeds.flags["C_CONTIGUOUS"]:
-        raise TypeError("grind: seeds must be a C-contiguous numpy uint64 array")
-    if seeds.ndim != 3 or seeds.shape[1:] != (WIDTH, 4):
-        raise ValueError("grind: seeds must have shape [n, %d, 4], got %r" % (WIDTH, seeds.shape))
+    n = _host_u64(seeds, "grind", (WIDTH, 4)).shape[0]
     for name, v in (("word", word), ("out_idx", out_idx)):
         if not isinstance(v, int) or not 0 <= v < WIDTH:
             raise ValueError("grind: %s must be 0 .. %d, got %r" % (name, WIDTH - 1, v))
@@ -1191,34 +1078,20 @@ def grind(seeds: np.ndarray, word: int, out_idx: int, target: int, first_nonce: 
     if not isinstance(first_nonce, int) or not isinstance(max_nonces, int) or first_nonce < 0 or max_nonces < 0 or \
             first_nonce + max_nonces > 1 << 64 or max_nonces >= 1 << 64:
         raise ValueError("grind: the nonce range [%r, %r + %r) does not lie in [0, 2^64)" % (first_nonce, first_nonce, max_nonces))
-    n = seeds.shape[0]
     if n > _lib.GRIND_MAX_JOBS:
         raise ValueError("grind: at most %d jobs per call, got %d" % (_lib.GRIND_MAX_JOBS, n))
     nonces = np.zeros(n, dtype=np.uint64)
     found = np.zeros(n, dtype=np.uint8)
-    tgt = (ctypes.c_uint64 * 4)(*[(target >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(4)])
-    check(_lib.lib().hades252_grind(_ptr(seeds), n, word, out_idx, tgt, first_nonce, max_nonces, _ptr(nonces), _ptr(found)),
-          "grind")
+    check(_lib.lib().hades252_grind(_ptr(seeds), n, word, out_idx, _tag_arr(target), first_nonce, max_nonces, _ptr(nonces),
+                                    _ptr(found)), "grind")
     return nonces, found.astype(bool)
-
-
-ROUNDS_TOTAL = TOTAL_FULL_ROUNDS + PARTIAL_ROUNDS          # HADES252_ROUNDS_TOTAL
-
-
-def _inverse_input(where: str, a, tail: tuple) -> np.ndarray:
-    """Type, contiguity and shape of a host batch, as grind checks its seeds; -> a copy the library works on in place."""
-    if not isinstance(a, np.ndarray) or a.dtype != np.uint64 or not a.flags["C_CONTIGUOUS"]:
-        raise TypeError("%s: the input must be a C-contiguous numpy uint64 array" % where)
-    if a.ndim != 1 + len(tail) or a.shape[1:] != tail:
-        raise ValueError("%s: the input must have shape [n, %s], got %r" % (where, ", ".join(map(str, tail)), a.shape))
-    return a.copy()
 
 
 def perm_inverse_rounds(states: np.ndarray, round_hi: int, round_lo: int) -> np.ndarray:
     """``hades252_perm_inverse_rounds``: rounds round_hi - 1, ..., round_lo of the permutation undone on HOST numpy uint64
     states [n, 5, 4] (Montgomery limbs): the state after round round_hi - 1 in, the state after round round_lo - 1 (the
     permutation's input for round_lo = 0) out, as a new array."""
-    out = _inverse_input("perm_inverse_rounds", states, (WIDTH, 4))
+    out = _host_u64(states, "perm_inverse_rounds", (WIDTH, 4)).copy()
     for v in (round_hi, round_lo):
         if not isinstance(v, int) or isinstance(v, bool):
             raise ValueError("perm_inverse_rounds: a round number is an int, got %r" % (v,))
@@ -1231,7 +1104,7 @@ def perm_inverse_rounds(states: np.ndarray, round_hi: int, round_lo: int) -> np.
 def perm_inverse(states: np.ndarray) -> np.ndarray:
     """``hades252_perm_inverse_batch``: the preimages of HOST numpy uint64 states [n, 5, 4] under the permutation, as a new
     array: perm(perm_inverse(y)) == y."""
-    out = _inverse_input("perm_inverse", states, (WIDTH, 4))
+    out = _host_u64(states, "perm_inverse", (WIDTH, 4)).copy()
     check(_lib.lib().hades252_perm_inverse_batch(_ptr(out), out.shape[0]), "perm_inverse")
     return out
 
@@ -1239,17 +1112,22 @@ def perm_inverse(states: np.ndarray) -> np.ndarray:
 def fifth_root(scalars: np.ndarray) -> np.ndarray:
     """``hades252_fifth_root_batch``: x -> x^(1/5) on HOST numpy uint64 scalars [n, 4] (Montgomery limbs), as a new array: the
     inverse of quintic_s_box on independent scalars."""
-    out = _inverse_input("fifth_root", scalars, (4,))
+    out = _host_u64(scalars, "fifth_root", (4,)).copy()
     check(_lib.lib().hades252_fifth_root_batch(_ptr(out), out.shape[0]), "fifth_root")
     return out
 
 
-def _matrix_planes(where: str, planes, n_rows):
-    """Type, contiguity and shape of a column-major matrix [n_cols, plane_stride, 4]; -> (n_rows, n_cols, plane_stride)."""
+def _planes_shape(where: str, planes):
+    """Type, contiguity and shape of columns [n_cols, plane_stride, 4] of a column-major matrix; -> (n_cols, plane_stride)."""
     planes = _host_u64(planes, where)
     if planes.ndim != 3 or planes.shape[2] != 4:
         raise ValueError("%s: planes must have shape [n_cols, plane_stride, 4], got %r" % (where, planes.shape))
-    n_cols, stride = planes.shape[0], planes.shape[1]
+    return planes.shape[0], planes.shape[1]
+
+
+def _matrix_planes(where: str, planes, n_rows):
+    """A whole column-major matrix and the rows of it that count; -> (n_rows, n_cols, plane_stride)."""
+    n_cols, stride = _planes_shape(where, planes)
     if not 1 <= n_cols <= _lib.MATRIX_MAX_COLS:
         raise ValueError("%s: 1 .. %d columns, got %d" % (where, _lib.MATRIX_MAX_COLS, n_cols))
     if n_rows is None:
@@ -1274,13 +1152,12 @@ def _matrix_modes(where: str, pad_mode, out_idx=1):
         raise ValueError("%s: out_idx must be 0 .. %d, got %r" % (where, WIDTH - 1, out_idx))
 
 
-def _matrix_pad(where: str, pad, depth: int):
-    if pad is None:
-        return None
-    pad = _host_u64(pad, where)
-    if pad.size != depth * 4:
-        raise ValueError("%s: the padding table needs %d digests" % (where, depth))
-    return _ptr(pad)
+def _commit_outputs(n_rows: int, nodes: int, want_digests: bool, want_tree: bool):
+    """What a commit call fills and returns: -> ((digests [n_rows, 4] or None, tree [nodes, 4] or None, root [4]), their
+    pointers)."""
+    outs = (np.zeros((n_rows, 4), dtype=np.uint64) if want_digests else None,
+            np.zeros((nodes, 4), dtype=np.uint64) if want_tree else None, np.zeros(4, dtype=np.uint64))
+    return outs, [None if a is None else _ptr(a) for a in outs]
 
 
 def matrix_row_digests_host(planes: np.ndarray, capacity_mont: int, pad_mode: int = 1, n_rows: int | None = None) -> np.ndarray:
@@ -1305,14 +1182,11 @@ def matrix_commit_host(planes: np.ndarray, capacity_mont: int, arity: int, tag_m
     n_rows, n_cols, stride = _matrix_planes(where, planes, n_rows)
     depth, nodes = _matrix_tree_shape(where, n_rows, arity)
     _matrix_modes(where, pad_mode, out_idx)
-    pptr = _matrix_pad(where, pad, depth)
-    digests = np.zeros((n_rows, 4), dtype=np.uint64) if want_digests else None
-    tree = np.zeros((nodes, 4), dtype=np.uint64) if want_tree else None
-    root = np.zeros(4, dtype=np.uint64)
+    pptr = _host_pad(where, pad, depth)
+    outs, out_ptrs = _commit_outputs(n_rows, nodes, want_digests, want_tree)
     check(_lib.lib().hades252_matrix_commit(_ptr(planes), n_rows, n_cols, stride, _tag_arr(capacity_mont), pad_mode, arity,
-                                            _tag_arr(tag_mont), out_idx, pptr, None if digests is None else _ptr(digests),
-                                            None if tree is None else _ptr(tree), _ptr(root)), where)
-    return digests, tree, root
+                                            _tag_arr(tag_mont), out_idx, pptr, *out_ptrs), where)
+    return outs
 
 
 def matrix_open_host(planes: np.ndarray, digests: np.ndarray, tree: np.ndarray, arity: int, indices,
@@ -1325,7 +1199,7 @@ def matrix_open_host(planes: np.ndarray, digests: np.ndarray, tree: np.ndarray, 
     digests, tree = _host_u64(digests, where), _host_u64(tree, where)
     if digests.size != n_rows * 4 or tree.size != nodes * 4:
         raise ValueError("%s: need %d row digests and a tree of %d digests" % (where, n_rows, nodes))
-    pptr = _matrix_pad(where, pad, depth)
+    pptr = _host_pad(where, pad, depth)
     idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
     rows = np.zeros((idx.size, n_cols, 4), dtype=np.uint64)
     paths = np.zeros((idx.size, depth, arity - 1, 4), dtype=np.uint64)
@@ -1387,14 +1261,12 @@ class MatrixStream:
         every plane.  ``n_rows``, when given, must be the stream's.  Synchronous; g = 0 is a no-op."""
         where = "MatrixStream.absorb"
         h = self._handle(where)
-        planes = _host_u64(planes, where)
-        if planes.ndim != 3 or planes.shape[2] != 4:
-            raise ValueError("%s: planes must have shape [n_cols, plane_stride, 4], got %r" % (where, planes.shape))
+        n_cols, stride = _planes_shape(where, planes)
         if n_rows is not None and n_rows != self.n_rows:
             raise ValueError("%s: the stream has %d rows, got n_rows = %r" % (where, self.n_rows, n_rows))
-        if planes.shape[1] < self.n_rows:
-            raise ValueError("%s: planes of %d rows for a stream of %d" % (where, planes.shape[1], self.n_rows))
-        check(_lib.lib().hades252_matstream_absorb(h, _ptr(planes), planes.shape[0], planes.shape[1]), where)
+        if stride < self.n_rows:
+            raise ValueError("%s: planes of %d rows for a stream of %d" % (where, stride, self.n_rows))
+        check(_lib.lib().hades252_matstream_absorb(h, _ptr(planes), n_cols, stride), where)
         return self
 
     @property
@@ -1421,14 +1293,10 @@ class MatrixStream:
         h = self._handle(where)
         depth, nodes = _matrix_tree_shape(where, self.n_rows, arity)
         _matrix_modes(where, pad_mode, out_idx)
-        pptr = _matrix_pad(where, pad, depth)
-        digests = np.zeros((self.n_rows, 4), dtype=np.uint64) if want_digests else None
-        tree = np.zeros((nodes, 4), dtype=np.uint64) if want_tree else None
-        root = np.zeros(4, dtype=np.uint64)
-        check(_lib.lib().hades252_matstream_commit(h, pad_mode, arity, _tag_arr(tag_mont), out_idx, pptr,
-                                                   None if digests is None else _ptr(digests),
-                                                   None if tree is None else _ptr(tree), _ptr(root)), where)
-        return digests, tree, root
+        pptr = _host_pad(where, pad, depth)
+        outs, out_ptrs = _commit_outputs(self.n_rows, nodes, want_digests, want_tree)
+        check(_lib.lib().hades252_matstream_commit(h, pad_mode, arity, _tag_arr(tag_mont), out_idx, pptr, *out_ptrs), where)
+        return outs
 
     def close(self) -> None:
         """Frees what the stream holds on the device; closing twice is fine."""
@@ -1454,27 +1322,20 @@ GEN_SEED = 0x4861646573323532
 
 def gen_b(n_elems: int, device, first_elem: int = 0, seed: int = GEN_SEED, out=None):
     """Generator B on device: n_elems scalars starting at global element index."""
-    import torch
-    out = torch.empty((n_elems, 4), dtype=torch.int64, device=device) if out is None else out
-    with torch.cuda.device(out.device):
-        check(_lib.lib().hades252_gen_b_dev(out.data_ptr(), first_elem, n_elems, seed, _stream_ptr(out.device)),
-              "gen_b")
+    out = _dev_empty(device, n_elems, 4) if out is None else out
+    _dev_call("gen_b", out.device, "hades252_gen_b_dev", out.data_ptr(), first_elem, n_elems, seed)
     return out
 
 
 def gen_a(n_elems: int, device, first_elem: int = 0):
-    import torch
-    out = torch.empty((n_elems, 4), dtype=torch.int64, device=device)
-    with torch.cuda.device(out.device):
-        check(_lib.lib().hades252_gen_a_dev(out.data_ptr(), first_elem, n_elems, _stream_ptr(out.device)), "gen_a")
+    out = _dev_empty(device, n_elems, 4)
+    _dev_call("gen_a", out.device, "hades252_gen_a_dev", out.data_ptr(), first_elem, n_elems)
     return out
 
 
 def digest(t, first_index: int = 0):
     """256-bit position-sensitive digest of a device buffer (4 python ints)."""
-    import torch
     ptr, n, dev = _dev_buffer(t, 8, "digest")
-    out = torch.empty(4, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        check(_lib.lib().hades252_digest_dev(ptr, first_index, n, out.data_ptr(), _stream_ptr(dev)), "digest")
+    out = _dev_empty(dev, 4)
+    _dev_call("digest", dev, "hades252_digest_dev", ptr, first_index, n, out.data_ptr())
     return [int(v) & 0xFFFFFFFFFFFFFFFF for v in out.cpu().tolist()]
