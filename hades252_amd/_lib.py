@@ -31,6 +31,7 @@ SAFE_MAX_WORDS = 1 << 20
 SAFE_ABSORB = 1 << 31
 GRIND_MAX_JOBS = 65535
 MATRIX_MAX_COLS = 4096
+MMCS_MAX_GROUPS = 32
 
 # every symbol include/hades252.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -173,6 +174,15 @@ SIGNATURES = {
     "hades252_matstream_commit": (c_int, [c_void_p, c_int, c_int, POINTER(c_uint64), c_int, c_void_p, c_void_p, c_void_p,
                                           c_void_p]),
     "hades252_matstream_close": (c_int, [c_void_p]),
+    "hades252_mmcs_new": (c_int, [POINTER(c_void_p), POINTER(c_uint64)]),
+    "hades252_mmcs_absorb": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t]),
+    "hades252_mmcs_cols": (c_int, [c_void_p, c_size_t, POINTER(c_uint64)]),
+    "hades252_mmcs_commit": (c_int, [c_void_p, c_int, c_int, POINTER(c_uint64), POINTER(c_uint64), c_int, c_void_p, c_void_p]),
+    "hades252_mmcs_free": (c_int, [c_void_p]),
+    "hades252_mmcs_tree_bytes": (c_size_t, [c_size_t, c_int]),
+    "hades252_mmcs_open": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_void_p]),
+    "hades252_mmcs_verify": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int,
+                                     POINTER(c_uint64), c_int, POINTER(c_uint64), POINTER(c_uint64), c_int, c_void_p]),
     "hades252_gen_b_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_uint64, c_void_p]),
     "hades252_gen_a_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_void_p]),
     "hades252_digest_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_void_p, c_void_p]),

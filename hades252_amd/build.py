@@ -54,7 +54,12 @@ MATRIX_DEPS = ["kernels_matrix.hpp", "host_matrix.hpp"]
 # device_source_hash and perm_fast_hash.  The host simulation runs the kernels from a driver of its own
 # (tests/hostsim_matrix_stream).
 MATRIX_STREAM_DEPS = ["kernels_matrix_stream.hpp", "host_matrix_stream.hpp"]
-DEPS = HOST_DEPS + LAUNCH_POLICY_DEPS + DEVICE_DEPS + UNRECORDED_KERNEL_DEPS + GRIND_DEPS + INVERSE_DEPS + MATRIX_DEPS + MATRIX_STREAM_DEPS + [os.path.join("..", "..", "include", "hades252.h")]
+# mixed-height matrix commitments (several matrices of different heights under one tree, whole openings verified in one
+# launch): their kernels and host calls, host pointers only, on top of the streams of MATRIX_STREAM_DEPS.  As those: rebuilt
+# like every other source (DEPS), outside device_source_hash and perm_fast_hash.  The host simulation runs the kernels from
+# a driver of its own (tests/hostsim_mmcs).
+MMCS_DEPS = ["kernels_mmcs.hpp", "host_mmcs.hpp"]
+DEPS = HOST_DEPS + LAUNCH_POLICY_DEPS + DEVICE_DEPS + UNRECORDED_KERNEL_DEPS + GRIND_DEPS + INVERSE_DEPS + MATRIX_DEPS + MATRIX_STREAM_DEPS + MMCS_DEPS + [os.path.join("..", "..", "include", "hades252.h")]
 # what the dominant kernel (k_perm_fast) is made of: profiles recorded for it stay valid while these are unchanged
 PERM_FAST_DEPS = ["fr32.hpp", "staging.hpp", "hades_fast.hpp", "k_perm_fast.hpp"]
 # ... plus these tables of hades_constants.inc (other kernels' tables may change without touching k_perm_fast)

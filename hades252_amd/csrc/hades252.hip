@@ -38,6 +38,7 @@ using namespace hades;
 #include "kernels_inverse.hpp"
 #include "kernels_matrix.hpp"
 #include "kernels_matrix_stream.hpp"
+#include "kernels_mmcs.hpp"
 #include "kernels_witness.hpp"
 #include "kernels_aux.hpp"
 
@@ -63,4 +64,5 @@ using namespace hades;
 #include "host_inverse.hpp"
 #include "host_matrix.hpp"
 #include "host_matrix_stream.hpp"
+#include "host_mmcs.hpp"
 #include "host_cipher.hpp"

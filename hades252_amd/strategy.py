@@ -1317,6 +1317,178 @@ class MatrixStream:
             pass
 
 
+def _mmcs_depth(where: str, max_rows, arity) -> int:
+    """D of a tallest height ``max_rows`` = arity^D (D >= 1, at most 2^30 rows), without the library."""
+    if not isinstance(arity, int) or isinstance(arity, bool) or not 2 <= arity <= 4:
+        raise ValueError("%s: arity 2..4, got %r" % (where, arity))
+    if not isinstance(max_rows, int) or isinstance(max_rows, bool) or not arity <= max_rows <= 1 << 30:
+        raise ValueError("%s: the tallest height must be arity .. 2^30, got %r" % (where, max_rows))
+    depth, n = 0, max_rows
+    while n > 1:
+        if n % arity:
+            raise ValueError("%s: %d is not a power of the arity %d" % (where, max_rows, arity))
+        n //= arity
+        depth += 1
+    return depth
+
+
+def mmcs_tree_bytes(max_rows: int, arity: int) -> int:
+    """``hades252_mmcs_tree_bytes``: bytes of the tree of a mixed-height commitment whose tallest group has ``max_rows`` rows
+    (every level from the tallest group's digests to the root); 0 for an invalid shape."""
+    return int(_lib.lib().hades252_mmcs_tree_bytes(max_rows, arity))
+
+
+def mmcs_open(tree: np.ndarray, max_rows: int, arity: int, indices) -> np.ndarray:
+    """``hades252_mmcs_open``: paths [q, depth, arity - 1, 4] for the indices ``indices`` from the tree Mmcs.commit returned.
+    Plain host code: no device is touched.  An index >= max_rows gives zeros."""
+    where = "mmcs_open"
+    depth = _mmcs_depth(where, max_rows, arity)
+    nodes = sum(arity ** l for l in range(depth + 1))
+    if _host_u64(tree, where).size != nodes * 4:
+        raise ValueError("%s: need a tree of %d digests" % (where, nodes))
+    idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+    paths = np.zeros((idx.size, depth, arity - 1, 4), dtype=np.uint64)
+    check(_lib.lib().hades252_mmcs_open(_ptr(tree), max_rows, arity, _ptr(idx), idx.size, _ptr(paths)), where)
+    return paths
+
+
+def mmcs_verify(rows: np.ndarray, heights, cols, indices, paths: np.ndarray, arity: int, capacity_mont: int, tag_mont: int,
+                inject_tag_mont: int, pad_mode: int = 1, out_idx: int = 1) -> np.ndarray:
+    """``hades252_mmcs_verify``: roots [q, 4] recomputed from the openings of a mixed-height commitment, one launch per chunk
+    of queries: ``rows`` [q, sum(cols), 4] holds, per query, the opened rows of all groups concatenated, tallest first;
+    ``heights`` / ``cols`` describe the groups (strictly decreasing powers of the arity); ``paths`` [q, depth, arity - 1, 4]
+    is what mmcs_open returns.  The caller compares the roots with the one it trusts."""
+    where = "mmcs_verify"
+    rows, paths = _host_u64(rows, where), _host_u64(paths, where)
+    hs = np.ascontiguousarray(heights, dtype=np.uint64).reshape(-1)
+    cs = np.ascontiguousarray(cols, dtype=np.uint64).reshape(-1)
+    if not 1 <= hs.size <= _lib.MMCS_MAX_GROUPS or cs.size != hs.size:
+        raise ValueError("%s: 1 .. %d groups, one height and one column count each" % (where, _lib.MMCS_MAX_GROUPS))
+    depth = _mmcs_depth(where, int(hs[0]), arity)
+    for g in range(hs.size):
+        if g > 0:
+            if not 1 <= int(hs[g]) < int(hs[g - 1]):
+                raise ValueError("%s: heights must be strictly decreasing, got %r" % (where, hs.tolist()))
+            n = int(hs[g])
+            while n > 1 and n % arity == 0:
+                n //= arity
+            if n != 1:
+                raise ValueError("%s: %d is not a power of the arity %d" % (where, int(hs[g]), arity))
+        if not 1 <= int(cs[g]) <= 1 << 30:
+            raise ValueError("%s: 1 .. 2^30 columns per group, got %d" % (where, int(cs[g])))
+    total = int(cs.sum())
+    if rows.ndim != 3 or rows.shape[1:] != (total, 4):
+        raise ValueError("%s: rows must have shape [q, %d, 4], got %r" % (where, total, rows.shape))
+    q = rows.shape[0]
+    if paths.ndim != 4 or paths.shape != (q, depth, arity - 1, 4):
+        raise ValueError("%s: paths must have shape [%d, %d, %d, 4], got %r" % (where, q, depth, arity - 1, paths.shape))
+    _matrix_modes(where, pad_mode, out_idx)
+    idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+    if idx.size != q:
+        raise ValueError("%s: %d indices for %d openings" % (where, idx.size, q))
+    roots = np.zeros((q, 4), dtype=np.uint64)
+    check(_lib.lib().hades252_mmcs_verify(_ptr(rows), _ptr(hs), _ptr(cs), hs.size, _ptr(idx), _ptr(paths), q, arity,
+                                          _tag_arr(capacity_mont), pad_mode, _tag_arr(tag_mont), _tag_arr(inject_tag_mont),
+                                          out_idx, _ptr(roots)), where)
+    return roots
+
+
+class Mmcs:
+    """``hades252_mmcs_*``: ONE commitment to several column-major matrices of different heights.  The tree sits over the
+    tallest matrix's row digests and the row digests of each shorter matrix are hashed into the level whose size equals its
+    height: one root, one path per query.  ``absorb`` feeds the group of the planes' height (created at first use; calls for
+    different heights interleave freely), ``commit`` is non-destructive.  HOST numpy arrays in and out; a context manager::
+
+        with Mmcs(capacity_mont) as mc:
+            mc.absorb(trace)                  # uint64 [g, plane_stride, 4]; n_rows defaults to plane_stride
+            mc.absorb(quotient)               # another height
+            tree, root = mc.commit(arity, tag_mont, inject_tag_mont)
+    """
+
+    def __init__(self, capacity_mont: int):
+        self._h = None
+        h = ctypes.c_void_p()
+        check(_lib.lib().hades252_mmcs_new(ctypes.byref(h), _tag_arr(capacity_mont)), "Mmcs")
+        self._h = h
+        self._heights = []
+
+    def _handle(self, where: str):
+        if self._h is None:
+            raise ValueError("%s: the commitment is closed" % where)
+        return self._h
+
+    @staticmethod
+    def _rows(where: str, n_rows):
+        if not isinstance(n_rows, int) or isinstance(n_rows, bool) or not 1 <= n_rows <= 1 << 30:
+            raise ValueError("%s: n_rows must be 1 .. 2^30, got %r" % (where, n_rows))
+        return n_rows
+
+    def absorb(self, planes: np.ndarray, n_rows: int | None = None) -> "Mmcs":
+        """The next columns of the group of height ``n_rows`` (default: the planes' stride): ``planes`` uint64
+        [g, plane_stride, 4] (Montgomery limbs), rows 0 .. n_rows - 1 of every plane.  Synchronous; g = 0 is a no-op."""
+        where = "Mmcs.absorb"
+        h = self._handle(where)
+        n_cols, stride = _planes_shape(where, planes)
+        n_rows = self._rows(where, stride if n_rows is None else n_rows)
+        if stride < n_rows:
+            raise ValueError("%s: planes of %d rows for a group of %d" % (where, stride, n_rows))
+        if n_cols and n_rows not in self._heights and len(self._heights) == _lib.MMCS_MAX_GROUPS:
+            raise ValueError("%s: at most %d distinct heights" % (where, _lib.MMCS_MAX_GROUPS))
+        check(_lib.lib().hades252_mmcs_absorb(h, _ptr(planes), n_rows, n_cols, stride), where)
+        if n_cols and n_rows not in self._heights:
+            self._heights.append(n_rows)
+        return self
+
+    def cols(self, n_rows: int) -> int:
+        """Columns absorbed so far for the height ``n_rows``; 0: no such group."""
+        where = "Mmcs.cols"
+        h, n_rows, n = self._handle(where), self._rows(where, n_rows), ctypes.c_uint64()
+        check(_lib.lib().hades252_mmcs_cols(h, n_rows, ctypes.byref(n)), where)
+        return int(n.value)
+
+    @property
+    def heights(self):
+        """The groups' heights, tallest first."""
+        return sorted(self._heights, reverse=True)
+
+    def commit(self, arity: int, tag_mont: int, inject_tag_mont: int, pad_mode: int = 1, out_idx: int = 1,
+               want_tree: bool = True):
+        """(tree [nodes, 4] or None, root [4]) of everything absorbed so far: every level from the tallest group's row
+        digests to the root, after the injections; the commitment is left as it is."""
+        where = "Mmcs.commit"
+        h = self._handle(where)
+        if not self._heights:
+            raise ValueError("%s: nothing absorbed yet" % where)
+        depth = _mmcs_depth(where, max(self._heights), arity)
+        for n in self._heights:
+            if n > 1:                                                    # (a group of one row sits at the root)
+                _mmcs_depth(where, n, arity)
+        _matrix_modes(where, pad_mode, out_idx)
+        tree = np.zeros((sum(arity ** l for l in range(depth + 1)), 4), dtype=np.uint64) if want_tree else None
+        root = np.zeros(4, dtype=np.uint64)
+        check(_lib.lib().hades252_mmcs_commit(h, pad_mode, arity, _tag_arr(tag_mont), _tag_arr(inject_tag_mont), out_idx,
+                                              None if tree is None else _ptr(tree), _ptr(root)), where)
+        return tree, root
+
+    def close(self) -> None:
+        """Frees what the commitment holds on the device; closing twice is fine."""
+        h, self._h = self._h, None
+        if h is not None:
+            _lib.lib().hades252_mmcs_free(h)
+
+    def __enter__(self) -> "Mmcs":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 GEN_SEED = 0x4861646573323532
 
 

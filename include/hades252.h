@@ -747,6 +747,84 @@ int hades252_matstream_commit(void *ms, int pad_mode, int arity, const uint64_t 
                               uint64_t *digests, uint64_t *tree, uint64_t root[4]);
 int hades252_matstream_close(void *ms);
 
+/* ---- mixed-height matrix commitments: one root, fused batch verification (f14) ---- CONVENTION UNPINNED
+ * A prover holds several matrices of different heights (a trace, its extension, quotient and lookup tables) and answers every
+ * query index in all of them.  Instead of one tree, one root and one path per matrix (f12 / f13), ONE tree sits over the
+ * tallest matrix, and the row digests of each shorter matrix are hashed into the level whose size equals its height: one
+ * root, one path per query.  Everything is defined through what the library already computes (capacity, padding and the
+ * two tags are parameters, still unpinned).  With a the arity (2 .. 4):
+ *   groups    G <= HADES252_MMCS_MAX_GROUPS groups of heights h_0 > h_1 > ... > h_{G-1}, each h_g = a^(d_g), D = d_0 >= 1.  A
+ *             group is every column absorbed for that height, in the order of the calls: an h_g x c_g matrix M_g.
+ *   leaf_g[r] what hades252_matrix_row_digests gives for row r of M_g with the commitment's capacity_mont and the commit's
+ *             pad_mode.
+ *   nodes     node_D[i] = leaf_0[i].  For l = D - 1 .. 0: node_l[i] is the parent hades252_merkle_level_dev gives for the
+ *             children node_{l+1}[a i .. a i + a - 1] with tag_mont and out_idx; if a group has d_g = l the node is then
+ *             replaced by perm([inject_tag, node_l[i], leaf_g[i], 0, 0])[out_idx] -- the parent hades252_merkle_level_dev
+ *             gives at arity 2 for the pair (node_l[i], leaf_g[i]) with tag = inject_tag_mont.  root = node_0[0].
+ *   tree      node_D, then node_{D-1}, ..., then the root: final values, after injection.  hades252_mmcs_tree_bytes(h_0, a)
+ *             = 32 (a^D + ... + a + 1), or 0 for an invalid shape (max_rows not a power of the arity, below the arity or
+ *             above 2^30).
+ *   opening   of index i < h_0: for every group its row i / (h_0 / h_g), which the caller gathers from its own planes, and
+ *             ONE path: exactly what hades252_merkle_open_dev writes for d_leaves = node_D, d_tree = the rest, n_leaves =
+ *             h_0 (D x (a - 1) siblings of 32 bytes).  An index >= h_0 yields an all-zero path.
+ * With one group the tree is that group's digests followed by the tree of hades252_matstream_commit, and the root is the same.
+ *   hades252_mmcs_new         a commitment with this capacity word; *out is the handle (NULL on any failure).
+ *   hades252_mmcs_absorb      the next n_cols columns of the group of height n_rows, layout and rules of
+ *                             hades252_matstream_absorb.  The group is created at first use: 160 bytes of state and 32 of
+ *                             digest per row on the device (hades252_trim does not free them).  Calls for different heights
+ *                             interleave freely.  Synchronous: the caller may reuse planes when it returns.
+ *   hades252_mmcs_cols        the columns absorbed so far for that height; 0: no such group.
+ *   hades252_mmcs_commit      NON-DESTRUCTIVE: every prefix can be committed and absorbing goes on.  tree
+ *                             (hades252_mmcs_tree_bytes(h_0, arity) bytes) may be NULL, root may not; the root is written on
+ *                             success only.  The digests never visit the host.
+ *   hades252_mmcs_free        frees the commitment; free(NULL) succeeds.
+ *   hades252_mmcs_open        paths from the tree commit returned: a plain host gather, no device.  paths_out: n_queries x D
+ *                             x (arity - 1) x 32 bytes.  Duplicate and unsorted indices are fine.
+ *   hades252_mmcs_verify      roots[t] = the root recomputed from opening t; the caller compares it with the root it trusts.
+ *                             rows is query-major: query t holds the opened rows of all groups concatenated, tallest first,
+ *                             cols[0] + ... + cols[n_groups - 1] scalars; paths as hades252_mmcs_open writes them.  Indices
+ *                             are not range-checked, as in hades252_merkle_verify_dev.
+ * Verification is ONE launch per chunk: lane t runs the whole chain of query t -- for each group the sponge blocks of its
+ * row (hades252_sponge_blocks(cols[g], pad_mode)), the injection (g > 0), the levels up to the next group's height --
+ * hades252_sponge_blocks summed over the groups + D + (G - 1) dependent permutations, where composing the existing calls
+ * takes a sponge launch per group and a verify launch per tree segment.  The queries travel in chunks of at most 2^18
+ * queries and 128 MiB of rows plus paths through two device buffers, chunk i + 1 copied while chunk i runs.  Commit runs
+ * the groups' finishing launches one after the other, then one launch per level down to the shortest group's (each picks its
+ * latency form by size), an injection launch where a group sits, and one tree build above.  Page-locked planes are
+ * recommended, as for f12.
+ * Host pointers only, like f10 to f13: no device-pointer form, no canonical-bytes form, no witness form, no latency form of
+ * the verification, no multiproofs, no row gather (the caller holds the planes).
+ * A commitment is used by one thread at a time and with the device current that was current at new (with another one the
+ * call is HADES252_ERR_INVALID_ARG); different commitments, and commitments alongside any other call of the library, are
+ * independent.
+ * Rules, all decided before the device is touched.  new: out or capacity_mont NULL is HADES252_ERR_INVALID_ARG; no device is
+ * HADES252_ERR_NO_DEVICE.  Every other call with a NULL handle is HADES252_ERR_INVALID_ARG, except free.  absorb: n_cols = 0
+ * is a no-op success, even with NULL planes, and creates nothing; n_rows outside 1 .. 2^30, NULL planes or planes that are
+ * not 8-byte aligned, plane_stride < n_rows, a byte count that overflows size_t, a column total that overflows uint64_t or
+ * a 33rd distinct height is HADES252_ERR_INVALID_ARG and allocates nothing.  commit: pad_mode other than 0 or 1, arity
+ * outside 2 .. 4, out_idx outside 0 .. 4, tag_mont, inject_tag_mont or root NULL, tree or root not 8-byte aligned, no group,
+ * a height that is not a power of the arity or a tallest height below the arity is HADES252_ERR_INVALID_ARG and leaves the
+ * handle exactly as it was.  open and verify: n_queries = 0 is a no-op success, even with NULL pointers; a NULL or
+ * misaligned pointer, an invalid shape (open: hades252_mmcs_tree_bytes is 0; verify: n_groups outside 1 .. 32, heights that
+ * are not strictly decreasing powers of the arity with heights[0] >= arity, cols[g] outside 1 .. 2^30), n_queries above 2^30
+ * for verify or a byte count that overflows size_t is HADES252_ERR_INVALID_ARG.
+ * A HIP failure inside a call returns HADES252_ERR_HIP and poisons the handle: every later absorb or commit returns
+ * HADES252_ERR_HIP without touching the device, cols still answers with the last good totals, free always works. */
+#define HADES252_MMCS_MAX_GROUPS 32
+int hades252_mmcs_new(void **out, const uint64_t capacity_mont[4]);
+int hades252_mmcs_absorb(void *mc, const uint64_t *planes, size_t n_rows, size_t n_cols, size_t plane_stride);
+int hades252_mmcs_cols(const void *mc, size_t n_rows, uint64_t *n_cols_so_far);
+int hades252_mmcs_commit(void *mc, int pad_mode, int arity, const uint64_t tag_mont[4], const uint64_t inject_tag_mont[4],
+                         int out_idx, uint64_t *tree, uint64_t root[4]);
+int hades252_mmcs_free(void *mc);
+size_t hades252_mmcs_tree_bytes(size_t max_rows, int arity);
+int hades252_mmcs_open(const uint64_t *tree, size_t max_rows, int arity, const uint64_t *indices, size_t n_queries,
+                       uint64_t *paths_out);
+int hades252_mmcs_verify(const uint64_t *rows, const uint64_t *heights, const uint64_t *cols, size_t n_groups,
+                         const uint64_t *indices, const uint64_t *paths, size_t n_queries, int arity,
+                         const uint64_t capacity_mont[4], int pad_mode, const uint64_t tag_mont[4],
+                         const uint64_t inject_tag_mont[4], int out_idx, uint64_t *roots);
+
 /* ---- synthetic inputs and digests (benchmark / verification plumbing) --------------------- */
 /* Generator B: scalar e (global element index first_elem + k) gets 4 splitmix64 limbs, top limb
  * masked to 62 bits (always < p); see DESIGN.md.  Stateless, so shards generate independently. */

@@ -342,6 +342,69 @@ public:
         return root;
     }
 };
+// Several column-major matrices of different heights under ONE tree (include/hades252.h, hades252_mmcs_*): the tree sits over
+// the tallest matrix and the row digests of each shorter one are hashed into the level whose size equals its height.  absorb
+// feeds the group of height n_rows (created at first use), commit is non-destructive.  Host pointers only.  Movable, frees
+// on destruction.  mmcs_open is plain host code (paths_out: n_queries x depth x (arity - 1)); mmcs_verify recomputes one
+// root per opening (rows: query-major, the groups' rows concatenated, tallest first) for the caller to compare.
+class Mmcs {
+    void *h_ = nullptr;
+
+public:
+    explicit Mmcs(const BlsScalar &capacity) { check(hades252_mmcs_new(&h_, capacity.limbs), "Mmcs"); }
+    Mmcs(const Mmcs &) = delete;
+    Mmcs &operator=(const Mmcs &) = delete;
+    Mmcs(Mmcs &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    Mmcs &operator=(Mmcs &&o) noexcept {
+        if (this != &o) {
+            close();
+            h_ = o.h_;
+            o.h_ = nullptr;
+        }
+        return *this;
+    }
+    ~Mmcs() { close(); }
+    void close() noexcept {
+        if (h_) (void)hades252_mmcs_free(h_);
+        h_ = nullptr;
+    }
+    // the next n_cols columns of the group of height n_rows: scalar (r, j) = planes[j * plane_stride + r]
+    void absorb(const BlsScalar *planes, std::size_t n_rows, std::size_t n_cols, std::size_t plane_stride) {
+        check(hades252_mmcs_absorb(h_, reinterpret_cast<const std::uint64_t *>(planes), n_rows, n_cols, plane_stride),
+              "Mmcs::absorb");
+    }
+    // columns absorbed so far for that height; 0: no such group
+    std::uint64_t cols(std::size_t n_rows) const {
+        std::uint64_t n = 0;
+        check(hades252_mmcs_cols(h_, n_rows, &n), "Mmcs::cols");
+        return n;
+    }
+    // tree (mmcs_tree_bytes(tallest height, arity) bytes) may be nullptr (not wanted); the root is returned
+    BlsScalar commit(bool pad_one, int arity, const BlsScalar &tag, const BlsScalar &inject_tag, int out_idx = 1,
+                     BlsScalar *tree = nullptr) {
+        BlsScalar root{};
+        check(hades252_mmcs_commit(h_, pad_one ? 1 : 0, arity, tag.limbs, inject_tag.limbs, out_idx,
+                                   reinterpret_cast<std::uint64_t *>(tree), root.limbs),
+              "Mmcs::commit");
+        return root;
+    }
+};
+inline std::size_t mmcs_tree_bytes(std::size_t max_rows, int arity) { return hades252_mmcs_tree_bytes(max_rows, arity); }
+inline void mmcs_open(const BlsScalar *tree, std::size_t max_rows, int arity, const std::uint64_t *indices, std::size_t n_queries,
+                      BlsScalar *paths_out) {
+    check(hades252_mmcs_open(reinterpret_cast<const std::uint64_t *>(tree), max_rows, arity, indices, n_queries,
+                             reinterpret_cast<std::uint64_t *>(paths_out)),
+          "mmcs_open");
+}
+inline void mmcs_verify(const BlsScalar *rows, const std::uint64_t *heights, const std::uint64_t *cols, std::size_t n_groups,
+                        const std::uint64_t *indices, const BlsScalar *paths, std::size_t n_queries, int arity,
+                        const BlsScalar &capacity, bool pad_one, const BlsScalar &tag, const BlsScalar &inject_tag, int out_idx,
+                        BlsScalar *roots) {
+    check(hades252_mmcs_verify(reinterpret_cast<const std::uint64_t *>(rows), heights, cols, n_groups, indices,
+                               reinterpret_cast<const std::uint64_t *>(paths), n_queries, arity, capacity.limbs, pad_one ? 1 : 0,
+                               tag.limbs, inject_tag.limbs, out_idx, reinterpret_cast<std::uint64_t *>(roots)),
+          "mmcs_verify");
+}
 // DEVICE memory, enqueued on `stream`: the whole pattern in one launch, or call by call on the 160-byte states of
 // hades252_sponge_init_dev with a caller-owned cursor (0 = fresh) that moves with every call.
 inline void safe_hash_dev(const void *d_in, std::size_t n_msgs, const std::uint32_t *calls, std::size_t n_calls,
