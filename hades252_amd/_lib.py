@@ -183,6 +183,12 @@ SIGNATURES = {
     "hades252_mmcs_open": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_void_p]),
     "hades252_mmcs_verify": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int,
                                      POINTER(c_uint64), c_int, POINTER(c_uint64), POINTER(c_uint64), c_int, c_void_p]),
+    "hades252_dmmcs_absorb": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "hades252_dmmcs_tree": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_size_t), POINTER(c_int)]),
+    "hades252_dmmcs_open": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
+                                    c_void_p, c_void_p]),
+    "hades252_dmmcs_verify": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int,
+                                      POINTER(c_uint64), c_int, POINTER(c_uint64), POINTER(c_uint64), c_int, c_void_p, c_void_p]),
     "hades252_gen_b_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_uint64, c_void_p]),
     "hades252_gen_a_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_void_p]),
     "hades252_digest_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_void_p, c_void_p]),

@@ -59,7 +59,12 @@ MATRIX_STREAM_DEPS = ["kernels_matrix_stream.hpp", "host_matrix_stream.hpp"]
 # like every other source (DEPS), outside device_source_hash and perm_fast_hash.  The host simulation runs the kernels from
 # a driver of its own (tests/hostsim_mmcs).
 MMCS_DEPS = ["kernels_mmcs.hpp", "host_mmcs.hpp"]
-DEPS = HOST_DEPS + LAUNCH_POLICY_DEPS + DEVICE_DEPS + UNRECORDED_KERNEL_DEPS + GRIND_DEPS + INVERSE_DEPS + MATRIX_DEPS + MATRIX_STREAM_DEPS + MMCS_DEPS + [os.path.join("..", "..", "include", "hades252.h")]
+# device-resident mixed-height commitments (the handle of MMCS_DEPS fed, opened and verified from device memory on the
+# caller's stream): two kernels and their host calls.  As MMCS_DEPS: rebuilt like every other source (DEPS), outside
+# device_source_hash and perm_fast_hash.  The host simulation runs the kernels from a driver of its own
+# (tests/hostsim_dmmcs).
+DMMCS_DEPS = ["kernels_dmmcs.hpp", "abi_dmmcs.hpp"]
+DEPS = HOST_DEPS + LAUNCH_POLICY_DEPS + DEVICE_DEPS + UNRECORDED_KERNEL_DEPS + GRIND_DEPS + INVERSE_DEPS + MATRIX_DEPS + MATRIX_STREAM_DEPS + MMCS_DEPS + DMMCS_DEPS + [os.path.join("..", "..", "include", "hades252.h")]
 # what the dominant kernel (k_perm_fast) is made of: profiles recorded for it stay valid while these are unchanged
 PERM_FAST_DEPS = ["fr32.hpp", "staging.hpp", "hades_fast.hpp", "k_perm_fast.hpp"]
 # ... plus these tables of hades_constants.inc (other kernels' tables may change without touching k_perm_fast)

@@ -39,6 +39,7 @@ using namespace hades;
 #include "kernels_matrix.hpp"
 #include "kernels_matrix_stream.hpp"
 #include "kernels_mmcs.hpp"
+#include "kernels_dmmcs.hpp"
 #include "kernels_witness.hpp"
 #include "kernels_aux.hpp"
 
@@ -65,4 +66,5 @@ using namespace hades;
 #include "host_matrix.hpp"
 #include "host_matrix_stream.hpp"
 #include "host_mmcs.hpp"
+#include "abi_dmmcs.hpp"
 #include "host_cipher.hpp"

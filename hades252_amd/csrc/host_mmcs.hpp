@@ -16,6 +16,8 @@ struct MmcsHandle {
     MatrixStreamHandle *groups[HADES252_MMCS_MAX_GROUPS] = {};
     uint8_t *d_tree = nullptr;
     size_t tree_cap = 0;
+    int tree_arity = 0;               // the tree of the last good commit: its arity and its tallest height (0: none)
+    size_t tree_rows = 0;
     bool poisoned = false;            // a HIP failure inside a call: nothing but cols and free works any more
 };
 
@@ -151,6 +153,7 @@ static int mmcs_commit_run(MmcsHandle *h, const int *order, const int *d, int pa
                            const uint64_t inject_tag_mont[4], int out_idx, uint64_t *tree, uint64_t *root) {
     const int G = h->n_groups, D = d[0];
     const size_t h0 = h->groups[order[0]]->n_rows, tree_bytes = hades252_mmcs_tree_bytes(h0, arity);
+    h->tree_rows = 0;                                                  // the tree is rewritten from here on
     if (h->tree_cap < tree_bytes) {
         if (h->d_tree) (void)hipFree(h->d_tree);
         h->d_tree = nullptr;
@@ -194,6 +197,8 @@ static int mmcs_commit_run(MmcsHandle *h, const int *order, const int *d, int pa
     TRY_CALL(call, F(F_MEMCPY, hipMemcpyAsync(got, h->d_tree + tree_bytes - 32, 32, hipMemcpyDeviceToHost, pp.s_k)));
     TRY_CALL(call, F(F_SYNC, hipStreamSynchronize(pp.s_k)));
     memcpy(root, got, 32);
+    h->tree_arity = arity;
+    h->tree_rows = h0;
     return call.finish(HADES252_OK);
 }
 
@@ -264,6 +269,34 @@ static void mmcs_launch_verify(int arity, hipStream_t s, const uint8_t *d_rows, 
 #undef HADES_LAUNCH_MMCS_VERIFY
 }
 
+// The shape of a batch of openings as both verification calls check it (n_groups is 1 .. 32 and arity 2 .. 4 already):
+// strictly falling powers of the arity from heights[0] >= arity, 1 .. 2^30 columns each, byte counts inside size_t.  -> the
+// group table of k_mmcs_verify, the columns of a query's row, the permutations of a chain, the depth and a path's bytes.
+struct MmcsShape {
+    MmcsGroups table = {};
+    size_t row_cols = 0, n_perms = 0, path_q = 0;
+    int depth = 0;
+};
+
+static bool mmcs_verify_shape(const uint64_t *heights, const uint64_t *cols, size_t n_groups, int arity, int pad_mode,
+                              size_t n_queries, MmcsShape &sh) {
+    int prev = -1;
+    for (size_t g = 0; g < n_groups; g++) {
+        const int d = mmcs_log(heights[g], arity);
+        if (d < 0 || (g == 0 ? d < 1 : d >= prev) || cols[g] < 1 || cols[g] > kMaxLaunchRecords) return false;
+        if (g > 0) sh.table.climb[g - 1] = (uint32_t)(prev - d);
+        sh.table.cols[g] = (uint32_t)cols[g];
+        sh.row_cols += (size_t)cols[g];
+        sh.n_perms += hades252_sponge_blocks((size_t)cols[g], pad_mode);
+        prev = d;
+    }
+    sh.table.climb[n_groups - 1] = (uint32_t)prev;
+    sh.depth = mmcs_log(heights[0], arity);
+    sh.n_perms += (size_t)sh.depth + (n_groups - 1);                   // S = sum of blocks_g + D + (G - 1)
+    sh.path_q = (size_t)sh.depth * (arity - 1) * 32;
+    return n_queries <= SIZE_MAX / 32 / sh.row_cols && n_queries <= SIZE_MAX / sh.path_q;
+}
+
 // roots[t] = the root recomputed from opening t.  The queries travel in chunks of at most 2^18 queries and
 // kMatrixTargetBytes of rows plus paths through the pooled pipe's two buffers: chunk i + 1 is copied on the copy stream
 // while chunk i runs on the kernel stream, which also carries its roots back; the host runs at most two chunks ahead.
@@ -278,23 +311,11 @@ int hades252_mmcs_verify(const uint64_t *rows, const uint64_t *heights, const ui
         host_misaligned(roots) || n_groups < 1 || n_groups > HADES252_MMCS_MAX_GROUPS || arity < 2 || arity > 4 ||
         (pad_mode != 0 && pad_mode != 1) || out_idx < 0 || out_idx >= 5 || n_queries > kMaxLaunchRecords)
         return HADES252_ERR_INVALID_ARG;
-    MmcsGroups table = {};
-    size_t row_cols = 0, n_perms = 0;
-    int prev = -1;
-    for (size_t g = 0; g < n_groups; g++) {
-        const int d = mmcs_log(heights[g], arity);
-        if (d < 0 || (g == 0 ? d < 1 : d >= prev) || cols[g] < 1 || cols[g] > kMaxLaunchRecords) return HADES252_ERR_INVALID_ARG;
-        if (g > 0) table.climb[g - 1] = (uint32_t)(prev - d);
-        table.cols[g] = (uint32_t)cols[g];
-        row_cols += (size_t)cols[g];
-        n_perms += hades252_sponge_blocks((size_t)cols[g], pad_mode);
-        prev = d;
-    }
-    table.climb[n_groups - 1] = (uint32_t)prev;
-    const int depth = mmcs_log(heights[0], arity);
-    n_perms += (size_t)depth + (n_groups - 1);                         // S = sum of blocks_g + D + (G - 1)
-    const size_t path_q = (size_t)depth * (arity - 1) * 32;
-    if (n_queries > SIZE_MAX / 32 / row_cols || n_queries > SIZE_MAX / path_q) return HADES252_ERR_INVALID_ARG;
+    MmcsShape sh;
+    if (!mmcs_verify_shape(heights, cols, n_groups, arity, pad_mode, n_queries, sh)) return HADES252_ERR_INVALID_ARG;
+    const MmcsGroups &table = sh.table;
+    const size_t row_cols = sh.row_cols, n_perms = sh.n_perms, path_q = sh.path_q;
+    const int depth = sh.depth;
     int rc = check_device();
     if (rc != HADES252_OK) return rc;
     size_t M = mmcs_forced_queries();

@@ -1352,14 +1352,8 @@ def mmcs_open(tree: np.ndarray, max_rows: int, arity: int, indices) -> np.ndarra
     return paths
 
 
-def mmcs_verify(rows: np.ndarray, heights, cols, indices, paths: np.ndarray, arity: int, capacity_mont: int, tag_mont: int,
-                inject_tag_mont: int, pad_mode: int = 1, out_idx: int = 1) -> np.ndarray:
-    """``hades252_mmcs_verify``: roots [q, 4] recomputed from the openings of a mixed-height commitment, one launch per chunk
-    of queries: ``rows`` [q, sum(cols), 4] holds, per query, the opened rows of all groups concatenated, tallest first;
-    ``heights`` / ``cols`` describe the groups (strictly decreasing powers of the arity); ``paths`` [q, depth, arity - 1, 4]
-    is what mmcs_open returns.  The caller compares the roots with the one it trusts."""
-    where = "mmcs_verify"
-    rows, paths = _host_u64(rows, where), _host_u64(paths, where)
+def _mmcs_groups(where: str, heights, cols, arity):
+    """The group tables of a verification, checked without the library: -> (heights, cols as uint64 arrays, depth)."""
     hs = np.ascontiguousarray(heights, dtype=np.uint64).reshape(-1)
     cs = np.ascontiguousarray(cols, dtype=np.uint64).reshape(-1)
     if not 1 <= hs.size <= _lib.MMCS_MAX_GROUPS or cs.size != hs.size:
@@ -1376,6 +1370,18 @@ def mmcs_verify(rows: np.ndarray, heights, cols, indices, paths: np.ndarray, ari
                 raise ValueError("%s: %d is not a power of the arity %d" % (where, int(hs[g]), arity))
         if not 1 <= int(cs[g]) <= 1 << 30:
             raise ValueError("%s: 1 .. 2^30 columns per group, got %d" % (where, int(cs[g])))
+    return hs, cs, depth
+
+
+def mmcs_verify(rows: np.ndarray, heights, cols, indices, paths: np.ndarray, arity: int, capacity_mont: int, tag_mont: int,
+                inject_tag_mont: int, pad_mode: int = 1, out_idx: int = 1) -> np.ndarray:
+    """``hades252_mmcs_verify``: roots [q, 4] recomputed from the openings of a mixed-height commitment, one launch per chunk
+    of queries: ``rows`` [q, sum(cols), 4] holds, per query, the opened rows of all groups concatenated, tallest first;
+    ``heights`` / ``cols`` describe the groups (strictly decreasing powers of the arity); ``paths`` [q, depth, arity - 1, 4]
+    is what mmcs_open returns.  The caller compares the roots with the one it trusts."""
+    where = "mmcs_verify"
+    rows, paths = _host_u64(rows, where), _host_u64(paths, where)
+    hs, cs, depth = _mmcs_groups(where, heights, cols, arity)
     total = int(cs.sum())
     if rows.ndim != 3 or rows.shape[1:] != (total, 4):
         raise ValueError("%s: rows must have shape [q, %d, 4], got %r" % (where, total, rows.shape))
@@ -1391,6 +1397,66 @@ def mmcs_verify(rows: np.ndarray, heights, cols, indices, paths: np.ndarray, ari
                                           _tag_arr(capacity_mont), pad_mode, _tag_arr(tag_mont), _tag_arr(inject_tag_mont),
                                           out_idx, _ptr(roots)), where)
     return roots
+
+
+def _dev_planes(where: str, part):
+    """One device matrix of a commitment: a CUDA int64 tensor [n_cols, plane_stride, 4] (Montgomery limbs), or a pair
+    (tensor, n_rows) when only rows 0 .. n_rows - 1 of every plane count; -> (pointer, n_rows, n_cols, stride, device)."""
+    t, n_rows = part if isinstance(part, tuple) and len(part) == 2 else (part, None)
+    ptr, _, dev = _dev_buffer(t, 32, where)
+    import torch
+    if t.dtype != torch.int64:
+        raise TypeError("%s: planes must be int64 tensors" % where)
+    if t.dim() != 3 or t.shape[2] != 4:
+        raise ValueError("%s: planes must have shape [n_cols, plane_stride, 4], got %r" % (where, tuple(t.shape)))
+    n_cols, stride = int(t.shape[0]), int(t.shape[1])
+    n_rows = Mmcs._rows(where, stride if n_rows is None else n_rows)
+    if stride < n_rows:
+        raise ValueError("%s: planes of %d rows for a group of %d" % (where, stride, n_rows))
+    return ptr, n_rows, n_cols, stride, dev
+
+
+def _dev_parts(where: str, parts):
+    """The four host arrays hades252_dmmcs_absorb / _open take for ``parts`` (all on one device); -> (arrays, device)."""
+    if not isinstance(parts, (list, tuple)) or not 1 <= len(parts) <= _lib.MMCS_MAX_GROUPS:
+        raise ValueError("%s: a list of 1 .. %d parts" % (where, _lib.MMCS_MAX_GROUPS))
+    got = [_dev_planes(where, part) for part in parts]
+    _same_device(where, got[0][4], *[g[4] for g in got[1:]])
+    arrays = [np.array([g[k] for g in got], dtype=np.uint64) for k in range(4)]
+    return arrays, got[0][4]
+
+
+def mmcs_verify_dev(rows_t, heights, cols, indices_t, paths_t, arity: int, capacity_mont: int, tag_mont: int,
+                    inject_tag_mont: int, pad_mode: int = 1, out_idx: int = 1):
+    """``hades252_dmmcs_verify``: mmcs_verify on DEVICE tensors, one launch on the current stream: ``rows_t`` int64
+    [q, sum(cols), 4], ``indices_t`` int64 [q], ``paths_t`` int64 [q, depth, arity - 1, 4] (what Mmcs.open_dev returns);
+    ``heights`` / ``cols`` stay host sequences.  -> roots int64 [q, 4] on that device; nothing is synchronised."""
+    where = "mmcs_verify_dev"
+    rptr, n_row_scalars, dev = _dev_buffer(rows_t, 32, where)
+    pptr, _, pdev = _dev_buffer(paths_t, 32, where)
+    iptr, q, idev = _dev_buffer(indices_t, 8, where)
+    _same_device(where, dev, pdev, idev)
+    hs, cs, depth = _mmcs_groups(where, heights, cols, arity)
+    total = int(cs.sum())
+    if tuple(rows_t.shape) != (q, total, 4) or rows_t.element_size() != 8:
+        raise ValueError("%s: rows must be 8-byte words of shape [%d, %d, 4], got %r" % (where, q, total, tuple(rows_t.shape)))
+    if tuple(paths_t.shape) != (q, depth, arity - 1, 4) or paths_t.element_size() != 8:
+        raise ValueError("%s: paths must be 8-byte words of shape [%d, %d, %d, 4], got %r"
+                         % (where, q, depth, arity - 1, tuple(paths_t.shape)))
+    if indices_t.dim() != 1 or indices_t.element_size() != 8:
+        raise ValueError("%s: indices must be %d 8-byte words" % (where, q))
+    _matrix_modes(where, pad_mode, out_idx)
+    roots = _dev_empty(dev, q, 4)
+    _dev_call(where, dev, "hades252_dmmcs_verify", rptr, _ptr(hs), _ptr(cs), hs.size, iptr, pptr, q, arity,
+              _tag_arr(capacity_mont), pad_mode, _tag_arr(tag_mont), _tag_arr(inject_tag_mont), out_idx, roots.data_ptr())
+    return roots
+
+
+class _DeviceWords:
+    """Device memory the library owns, as torch.as_tensor reads it (the CUDA array interface): int64 [n, 4]."""
+
+    def __init__(self, ptr: int, n: int):
+        self.__cuda_array_interface__ = {"shape": (n, 4), "typestr": "<i8", "data": (ptr, False), "version": 2}
 
 
 class Mmcs:
@@ -1469,6 +1535,59 @@ class Mmcs:
         check(_lib.lib().hades252_mmcs_commit(h, pad_mode, arity, _tag_arr(tag_mont), _tag_arr(inject_tag_mont), out_idx,
                                               None if tree is None else _ptr(tree), _ptr(root)), where)
         return tree, root
+
+    # ---- device memory (include/hades252.h, f15).  Everything below is enqueued on torch's current stream of the tensors'
+    # device and returns at once.  The library orders nothing between that stream and the streams absorb / commit / close
+    # run on: synchronise the stream before calling one of those on this commitment.
+    def absorb_dev(self, parts) -> "Mmcs":
+        """``hades252_dmmcs_absorb``: every part of ``parts`` -- a CUDA int64 tensor [g, plane_stride, 4] or a pair
+        (tensor, n_rows) -- is the next g columns of the group of its height; the heights are distinct and all parts run as
+        ONE launch.  A part with g = 0 is skipped."""
+        where = "Mmcs.absorb_dev"
+        h = self._handle(where)
+        (ptrs, rows, cols, strides), dev = _dev_parts(where, parts)
+        live = [int(r) for r, c in zip(rows, cols) if c]
+        if len(set(live)) != len(live):
+            raise ValueError("%s: the heights of one call must be distinct, got %r" % (where, rows.tolist()))
+        if len(set(live) | set(self._heights)) > _lib.MMCS_MAX_GROUPS:
+            raise ValueError("%s: at most %d distinct heights" % (where, _lib.MMCS_MAX_GROUPS))
+        _dev_call(where, dev, "hades252_dmmcs_absorb", h, _ptr(ptrs), _ptr(rows), _ptr(cols), _ptr(strides), len(parts))
+        self._heights += [r for r in live if r not in self._heights]
+        return self
+
+    def tree_dev(self, device=None):
+        """``hades252_dmmcs_tree``: a copy of the device tree of the last commit, int64 [nodes, 4] (the root is its last row),
+        made on the current stream of ``device`` (default: the current device) -> (tree, arity)."""
+        where = "Mmcs.tree_dev"
+        h = self._handle(where)
+        ptr, n_bytes, arity = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_int()
+        check(_lib.lib().hades252_dmmcs_tree(h, ctypes.byref(ptr), ctypes.byref(n_bytes), ctypes.byref(arity)), where)
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        return torch.as_tensor(_DeviceWords(ptr.value, n_bytes.value // 32), device=dev).clone(), int(arity.value)
+
+    def open_dev(self, parts, indices_t):
+        """``hades252_dmmcs_open``: (rows int64 [q, sum of the parts' columns, 4], paths int64 [q, depth, arity - 1, 4]) of the
+        indices ``indices_t`` (CUDA int64 [q]) from the committed matrices ``parts`` (as absorb_dev takes them, tallest
+        first) and the tree of the last commit: what mmcs_verify_dev reads.  An index >= the tallest height gives zeros."""
+        where = "Mmcs.open_dev"
+        h = self._handle(where)
+        (ptrs, rows, cols, strides), dev = _dev_parts(where, parts)
+        iptr, q, idev = _dev_buffer(indices_t, 8, where)
+        _same_device(where, dev, idev)
+        if indices_t.dim() != 1 or indices_t.element_size() != 8:
+            raise ValueError("%s: indices must be a vector of 8-byte words" % where)
+        hs = [int(r) for r in rows]
+        if any(a <= b for a, b in zip(hs, hs[1:])) or any(r not in self._heights for r in hs) or not cols.all():
+            raise ValueError("%s: the parts are groups of the commitment with columns, tallest first; got heights %r" % (where, hs))
+        ptr, n_bytes, arity = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_int()
+        check(_lib.lib().hades252_dmmcs_tree(h, ctypes.byref(ptr), ctypes.byref(n_bytes), ctypes.byref(arity)), where)
+        depth = _mmcs_depth(where, hs[0], int(arity.value))
+        out_rows = _dev_empty(dev, q, int(cols.sum()), 4)
+        paths = _dev_empty(dev, q, depth, int(arity.value) - 1, 4)
+        _dev_call(where, dev, "hades252_dmmcs_open", h, _ptr(ptrs), _ptr(rows), _ptr(cols), _ptr(strides), len(parts), iptr, q,
+                  out_rows.data_ptr(), paths.data_ptr())
+        return out_rows, paths
 
     def close(self) -> None:
         """Frees what the commitment holds on the device; closing twice is fine."""

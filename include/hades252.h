@@ -825,6 +825,67 @@ int hades252_mmcs_verify(const uint64_t *rows, const uint64_t *heights, const ui
                          const uint64_t capacity_mont[4], int pad_mode, const uint64_t tag_mont[4],
                          const uint64_t inject_tag_mont[4], int out_idx, uint64_t *roots);
 
+/* ---- device-resident mixed-height commitments: absorb, open and verify on the device (f15) ---- CONVENTION UNPINNED
+ * The commitment of f14, above, for a prover whose matrices already live in DEVICE memory: the same handle
+ * (hades252_mmcs_new), the same groups, tree, openings and roots, byte for byte, without a copy to the host and back.  The
+ * family is hades252_dmmcs_* ("d" for device-resident); hades252_mmcs_commit and hades252_mmcs_free stay the commit and the
+ * free, and one handle may be fed through hades252_mmcs_absorb and hades252_dmmcs_absorb in any mixture.  The last argument
+ * of absorb, open and verify is the caller's stream, as in every _dev call: the call enqueues there and returns; nothing is
+ * synchronised and nothing is downloaded.  Device pointers are 16-byte aligned; the arrays that describe the parts
+ * (d_planes, n_rows, n_cols, plane_strides, heights, cols) are HOST arrays and are not referenced after the call returns.
+ *   hades252_dmmcs_absorb   n_parts = 1 .. HADES252_MMCS_MAX_GROUPS parts.  Part p is a column-major device matrix, scalar
+ *                           (r, j) at d_planes[p] + (j * plane_strides[p] + r) * 32, absorbed as the next n_cols[p] columns
+ *                           of the group of height n_rows[p], by the rules of hades252_mmcs_absorb per part: the group is
+ *                           created at first use (its state planes are allocated and initialised before the call returns),
+ *                           a 33rd distinct height is refused, a part with n_cols[p] = 0 is skipped whatever else it
+ *                           holds.  The heights of one call are distinct.  All parts run as ONE launch: the grid is the
+ *                           blocks of all parts laid end to end, shortest part first, so the short groups' chains of
+ *                           permutations run beside the tall group's, not after it.  The column totals
+ *                           (hades252_mmcs_cols) move at enqueue time.  The planes are only read, and may be reused once
+ *                           the stream has passed the call.
+ *   hades252_dmmcs_tree     the device tree of the last successful hades252_mmcs_commit, in the layout of f14 (*tree_bytes
+ *                           = hades252_mmcs_tree_bytes(h_0, *arity); the root is its last 32 bytes), valid until the next
+ *                           commit or free: a device prover can hand it to hades252_merkle_open_dev and friends itself
+ *                           (d_leaves = the tree, d_tree = what follows its first h_0 digests).  No stream: nothing is enqueued.
+ *   hades252_dmmcs_open     the openings of n_queries device indices from that tree.  The handle keeps no matrix, only
+ *                           sponge states, so the caller passes the committed matrices in, tallest first, as absorb takes
+ *                           them: strictly falling heights, every one a group of the handle, the first the height h_0 of
+ *                           the committed tree.  d_rows: n_queries x (n_cols[0] + ... ) scalars, query-major, group g's row
+ *                           index / (h_0 / h_g), the groups concatenated tallest first; d_paths: n_queries x D x (arity - 1)
+ *                           digests, the paths of ONE call of hades252_merkle_open_dev on the tree -- exactly what
+ *                           hades252_mmcs_verify and hades252_dmmcs_verify read.  An index >= h_0 gives an all-zero row
+ *                           and an all-zero path: nothing outside the matrices and the tree is read.  Duplicate and
+ *                           unsorted indices are fine.  Two launches: the row gather and the paths.
+ *   hades252_dmmcs_verify   hades252_mmcs_verify with rows, indices, paths and roots in device memory (heights and cols
+ *                           stay host arrays, the shape rules are the same): ONE launch over all n_queries <= 2^30
+ *                           openings, straight from the caller's buffers -- no chunks, no staging buffer, no copy.
+ * Ordering rule.  The library orders NOTHING between a caller's stream and its own streams, on which the host-form calls of
+ * f14 run.  All hades252_dmmcs_* calls on one handle go on one stream, or the caller orders them; before any host-form call
+ * on that handle (hades252_mmcs_absorb, hades252_mmcs_commit, hades252_mmcs_free) the caller synchronises that stream.  The
+ * host-form calls are synchronous, so a hades252_dmmcs_* call enqueued after one returns sees its result.
+ * Rules, all decided before the device is touched; a refused call leaves the handle exactly as it was.  A NULL handle, a NULL
+ * array or output, n_parts outside 1 .. 32 is HADES252_ERR_INVALID_ARG.  absorb, per part with n_cols[p] > 0: n_rows[p]
+ * outside 1 .. 2^30, a NULL or misaligned d_planes[p], plane_strides[p] < n_rows[p], a byte count that overflows size_t, a
+ * column total that overflows uint64_t, a height that occurs twice in the call or a 33rd distinct height is
+ * HADES252_ERR_INVALID_ARG; a call whose parts are all skipped is a no-op success.  tree and open: no successful commit yet
+ * is HADES252_ERR_INVALID_ARG.  open: n_queries = 0 is a no-op success; n_rows[0] other than h_0, heights that do not fall
+ * strictly, a height that is no group of the handle, n_cols[p] outside 1 .. 2^30, the plane rules of absorb, a misaligned
+ * d_indices, d_rows or d_paths, n_queries x n_cols[p] above 2^30 or n_queries x D x (arity - 1) above 2^29 is
+ * HADES252_ERR_INVALID_ARG.  verify: the rules of hades252_mmcs_verify, with 16-byte alignment for d_rows, d_paths, d_roots.
+ * A handle is used with the device current that was current at new.  A launch that fails returns HADES252_ERR_HIP and
+ * poisons the handle, as in f14 (verify has no handle to poison).
+ * No witness form, no multiproofs, no device form of f12 / f13 on their own: one group of a commitment is that stream. */
+int hades252_dmmcs_absorb(void *mc, const void *const *d_planes, const uint64_t *n_rows, const uint64_t *n_cols,
+                          const uint64_t *plane_strides, size_t n_parts, void *stream);
+int hades252_dmmcs_tree(const void *mc, const void **d_tree, size_t *tree_bytes, int *arity);
+int hades252_dmmcs_open(const void *mc, const void *const *d_planes, const uint64_t *n_rows, const uint64_t *n_cols,
+                        const uint64_t *plane_strides, size_t n_parts, const uint64_t *d_indices, size_t n_queries,
+                        void *d_rows, void *d_paths, void *stream);
+int hades252_dmmcs_verify(const void *d_rows, const uint64_t *heights, const uint64_t *cols, size_t n_groups,
+                          const uint64_t *d_indices, const void *d_paths, size_t n_queries, int arity,
+                          const uint64_t capacity_mont[4], int pad_mode, const uint64_t tag_mont[4],
+                          const uint64_t inject_tag_mont[4], int out_idx, void *d_roots, void *stream);
+
 /* ---- synthetic inputs and digests (benchmark / verification plumbing) --------------------- */
 /* Generator B: scalar e (global element index first_elem + k) gets 4 splitmix64 limbs, top limb
  * masked to 62 bits (always < p); see DESIGN.md.  Stateless, so shards generate independently. */

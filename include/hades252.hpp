@@ -388,7 +388,41 @@ public:
               "Mmcs::commit");
         return root;
     }
+    // DEVICE memory, enqueued on `stream` (include/hades252.h, f15: the caller synchronises that stream before absorb,
+    // commit or the destructor run on this commitment).  n_parts column-major device matrices of distinct heights, all in
+    // one launch; the four arrays are host arrays.
+    void absorb_dev(const void *const *d_planes, const std::uint64_t *n_rows, const std::uint64_t *n_cols,
+                    const std::uint64_t *plane_strides, std::size_t n_parts, void *stream = nullptr) {
+        check(hades252_dmmcs_absorb(h_, d_planes, n_rows, n_cols, plane_strides, n_parts, stream), "Mmcs::absorb_dev");
+    }
+    // the device tree of the last commit (valid until the next commit or the destructor), its bytes and its arity
+    const void *tree_dev(std::size_t *tree_bytes = nullptr, int *arity = nullptr) const {
+        const void *tree = nullptr;
+        std::size_t bytes = 0;
+        int a = 0;
+        check(hades252_dmmcs_tree(h_, &tree, &bytes, &a), "Mmcs::tree_dev");
+        if (tree_bytes) *tree_bytes = bytes;
+        if (arity) *arity = a;
+        return tree;
+    }
+    // rows (query-major, the groups concatenated tallest first) and paths of n_queries device indices, from the committed
+    // matrices (tallest first) and the tree of the last commit: what mmcs_verify_dev reads
+    void open_dev(const void *const *d_planes, const std::uint64_t *n_rows, const std::uint64_t *n_cols,
+                  const std::uint64_t *plane_strides, std::size_t n_parts, const std::uint64_t *d_indices, std::size_t n_queries,
+                  void *d_rows, void *d_paths, void *stream = nullptr) const {
+        check(hades252_dmmcs_open(h_, d_planes, n_rows, n_cols, plane_strides, n_parts, d_indices, n_queries, d_rows, d_paths,
+                                  stream), "Mmcs::open_dev");
+    }
 };
+// mmcs_verify with rows, indices, paths and roots in DEVICE memory: one launch on `stream`
+inline void mmcs_verify_dev(const void *d_rows, const std::uint64_t *heights, const std::uint64_t *cols, std::size_t n_groups,
+                            const std::uint64_t *d_indices, const void *d_paths, std::size_t n_queries, int arity,
+                            const BlsScalar &capacity, bool pad_one, const BlsScalar &tag, const BlsScalar &inject_tag, int out_idx,
+                            void *d_roots, void *stream = nullptr) {
+    check(hades252_dmmcs_verify(d_rows, heights, cols, n_groups, d_indices, d_paths, n_queries, arity, capacity.limbs,
+                                pad_one ? 1 : 0, tag.limbs, inject_tag.limbs, out_idx, d_roots, stream),
+          "mmcs_verify_dev");
+}
 inline std::size_t mmcs_tree_bytes(std::size_t max_rows, int arity) { return hades252_mmcs_tree_bytes(max_rows, arity); }
 inline void mmcs_open(const BlsScalar *tree, std::size_t max_rows, int arity, const std::uint64_t *indices, std::size_t n_queries,
                       BlsScalar *paths_out) {
