@@ -32,6 +32,7 @@ SAFE_ABSORB = 1 << 31
 GRIND_MAX_JOBS = 65535
 MATRIX_MAX_COLS = 4096
 MMCS_MAX_GROUPS = 32
+LAYOUT_COLS, LAYOUT_ROWS = 0, 1     # HADES252_LAYOUT_*: column-major / row-major matrices (f16)
 
 # every symbol include/hades252.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -189,6 +190,10 @@ SIGNATURES = {
                                     c_void_p, c_void_p]),
     "hades252_dmmcs_verify": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int,
                                       POINTER(c_uint64), c_int, POINTER(c_uint64), POINTER(c_uint64), c_int, c_void_p, c_void_p]),
+    "hades252_rmmcs_absorb_rows": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t]),
+    "hades252_rmmcs_absorb_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "hades252_rmmcs_open_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
+                                       c_void_p, c_void_p, c_void_p]),
     "hades252_gen_b_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_uint64, c_void_p]),
     "hades252_gen_a_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_void_p]),
     "hades252_digest_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_void_p, c_void_p]),

@@ -64,7 +64,12 @@ MMCS_DEPS = ["kernels_mmcs.hpp", "host_mmcs.hpp"]
 # device_source_hash and perm_fast_hash.  The host simulation runs the kernels from a driver of its own
 # (tests/hostsim_dmmcs).
 DMMCS_DEPS = ["kernels_dmmcs.hpp", "abi_dmmcs.hpp"]
-DEPS = HOST_DEPS + LAUNCH_POLICY_DEPS + DEVICE_DEPS + UNRECORDED_KERNEL_DEPS + GRIND_DEPS + INVERSE_DEPS + MATRIX_DEPS + MATRIX_STREAM_DEPS + MMCS_DEPS + DMMCS_DEPS + [os.path.join("..", "..", "include", "hades252.h")]
+# row-major matrices for the commitments of MMCS_DEPS / DMMCS_DEPS (a layout per matrix, device and host form): two kernels
+# and their host calls, beside those of DMMCS_DEPS, which keep their own.  As DMMCS_DEPS: rebuilt like every other source
+# (DEPS), outside device_source_hash and perm_fast_hash.  The host simulation runs the kernels from a driver of its own
+# (tests/hostsim_rowmajor).
+ROWMAJOR_DEPS = ["kernels_rowmajor.hpp", "abi_rowmajor.hpp", "host_rowmajor.hpp"]
+DEPS = HOST_DEPS + LAUNCH_POLICY_DEPS + DEVICE_DEPS + UNRECORDED_KERNEL_DEPS + GRIND_DEPS + INVERSE_DEPS + MATRIX_DEPS + MATRIX_STREAM_DEPS + MMCS_DEPS + DMMCS_DEPS + ROWMAJOR_DEPS + [os.path.join("..", "..", "include", "hades252.h")]
 # what the dominant kernel (k_perm_fast) is made of: profiles recorded for it stay valid while these are unchanged
 PERM_FAST_DEPS = ["fr32.hpp", "staging.hpp", "hades_fast.hpp", "k_perm_fast.hpp"]
 # ... plus these tables of hades_constants.inc (other kernels' tables may change without touching k_perm_fast)

@@ -40,6 +40,7 @@ using namespace hades;
 #include "kernels_matrix_stream.hpp"
 #include "kernels_mmcs.hpp"
 #include "kernels_dmmcs.hpp"
+#include "kernels_rowmajor.hpp"
 #include "kernels_witness.hpp"
 #include "kernels_aux.hpp"
 
@@ -67,4 +68,6 @@ using namespace hades;
 #include "host_matrix_stream.hpp"
 #include "host_mmcs.hpp"
 #include "abi_dmmcs.hpp"
+#include "abi_rowmajor.hpp"
+#include "host_rowmajor.hpp"
 #include "host_cipher.hpp"

@@ -1416,13 +1416,43 @@ def _dev_planes(where: str, part):
     return ptr, n_rows, n_cols, stride, dev
 
 
-def _dev_parts(where: str, parts):
-    """The four host arrays hades252_dmmcs_absorb / _open take for ``parts`` (all on one device); -> (arrays, device)."""
+def _dev_rows(where: str, t):
+    """One ROW-MAJOR device matrix of a commitment: a CUDA int64 tensor [n_rows, n_cols, 4] (Montgomery limbs) whose scalars
+    are whole (stride(1) == 4, stride(2) == 1) and whose rows may lie further apart than their width -- a narrowed view
+    ``wide[:, a:b]`` -- with stride(0) // 4 the row stride; -> (pointer, n_rows, n_cols, stride, device)."""
+    import torch
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+        raise TypeError("%s: expected a CUDA torch.Tensor" % where)
+    if t.dtype != torch.int64:
+        raise TypeError("%s: rows must be int64 tensors" % where)
+    if t.dim() != 3 or t.shape[2] != 4:
+        raise ValueError("%s: rows must have shape [n_rows, n_cols, 4], got %r" % (where, tuple(t.shape)))
+    n_rows, n_cols = Mmcs._rows(where, int(t.shape[0])), int(t.shape[1])
+    stride = t.stride(0) // 4 if n_rows > 1 else n_cols                # (a single row has no stride to speak of)
+    if t.stride(2) != 1 or (n_cols > 1 and t.stride(1) != 4) or (n_rows > 1 and (t.stride(0) % 4 or stride < n_cols)):
+        raise ValueError("%s: rows of whole scalars side by side, a whole number of scalars apart; got strides %r" % (where, t.stride()))
+    if n_cols and t.data_ptr() % 16 != 0:
+        raise ValueError("%s: buffer must be 16-byte aligned" % where)
+    return t.data_ptr(), n_rows, n_cols, stride, t.device
+
+
+def _dev_parts(where: str, parts, layouts=None):
+    """The four host arrays hades252_dmmcs_absorb / _open take for ``parts`` (all on one device); -> (arrays, device).  With
+    ``layouts`` (one of _lib.LAYOUT_COLS / _lib.LAYOUT_ROWS per part: the part is what _dev_planes / _dev_rows takes) a
+    fifth array, uint32, for the ``_ex`` forms."""
     if not isinstance(parts, (list, tuple)) or not 1 <= len(parts) <= _lib.MMCS_MAX_GROUPS:
         raise ValueError("%s: a list of 1 .. %d parts" % (where, _lib.MMCS_MAX_GROUPS))
-    got = [_dev_planes(where, part) for part in parts]
+    if layouts is None:
+        got = [_dev_planes(where, part) for part in parts]
+    else:
+        if not isinstance(layouts, (list, tuple)) or len(layouts) != len(parts) or \
+                any(isinstance(l, bool) or l not in (_lib.LAYOUT_COLS, _lib.LAYOUT_ROWS) for l in layouts):
+            raise ValueError("%s: layouts is one of LAYOUT_COLS (0) / LAYOUT_ROWS (1) per part, got %r" % (where, layouts))
+        got = [(_dev_rows if l == _lib.LAYOUT_ROWS else _dev_planes)(where, part) for part, l in zip(parts, layouts)]
     _same_device(where, got[0][4], *[g[4] for g in got[1:]])
     arrays = [np.array([g[k] for g in got], dtype=np.uint64) for k in range(4)]
+    if layouts is not None:
+        arrays.append(np.array(layouts, dtype=np.uint32))
     return arrays, got[0][4]
 
 
@@ -1505,6 +1535,27 @@ class Mmcs:
             self._heights.append(n_rows)
         return self
 
+    def absorb_rows(self, rows: np.ndarray, n_cols: int | None = None) -> "Mmcs":
+        """``hades252_rmmcs_absorb_rows``: the next columns of the group of height n_rows from a ROW-major matrix: ``rows``
+        uint64 [n_rows, row_stride, 4] (Montgomery limbs), columns 0 .. n_cols - 1 of every row (default: all row_stride).
+        Synchronous; n_cols = 0 is a no-op.  No transpose is made anywhere."""
+        where = "Mmcs.absorb_rows"
+        h = self._handle(where)
+        rows = _host_u64(rows, where)
+        if rows.ndim != 3 or rows.shape[2] != 4:
+            raise ValueError("%s: rows must have shape [n_rows, row_stride, 4], got %r" % (where, rows.shape))
+        n_rows, stride = self._rows(where, rows.shape[0]), rows.shape[1]
+        if n_cols is None:
+            n_cols = stride
+        if not isinstance(n_cols, int) or isinstance(n_cols, bool) or not 0 <= n_cols <= stride:
+            raise ValueError("%s: n_cols must be 0 .. row_stride = %d, got %r" % (where, stride, n_cols))
+        if n_cols and n_rows not in self._heights and len(self._heights) == _lib.MMCS_MAX_GROUPS:
+            raise ValueError("%s: at most %d distinct heights" % (where, _lib.MMCS_MAX_GROUPS))
+        check(_lib.lib().hades252_rmmcs_absorb_rows(h, _ptr(rows), n_rows, n_cols, stride), where)
+        if n_cols and n_rows not in self._heights:
+            self._heights.append(n_rows)
+        return self
+
     def cols(self, n_rows: int) -> int:
         """Columns absorbed so far for the height ``n_rows``; 0: no such group."""
         where = "Mmcs.cols"
@@ -1539,19 +1590,24 @@ class Mmcs:
     # ---- device memory (include/hades252.h, f15).  Everything below is enqueued on torch's current stream of the tensors'
     # device and returns at once.  The library orders nothing between that stream and the streams absorb / commit / close
     # run on: synchronise the stream before calling one of those on this commitment.
-    def absorb_dev(self, parts) -> "Mmcs":
+    def absorb_dev(self, parts, layouts=None) -> "Mmcs":
         """``hades252_dmmcs_absorb``: every part of ``parts`` -- a CUDA int64 tensor [g, plane_stride, 4] or a pair
         (tensor, n_rows) -- is the next g columns of the group of its height; the heights are distinct and all parts run as
-        ONE launch.  A part with g = 0 is skipped."""
+        ONE launch.  A part with g = 0 is skipped.  With ``layouts`` (``hades252_rmmcs_absorb_ex``: LAYOUT_COLS or
+        LAYOUT_ROWS per part) a LAYOUT_ROWS part is a ROW-major matrix: a CUDA int64 tensor [n_rows, g, 4], possibly a
+        narrowed view of wider rows (stride(0) // 4 is its row stride, stride(1) == 4, stride(2) == 1)."""
         where = "Mmcs.absorb_dev"
         h = self._handle(where)
-        (ptrs, rows, cols, strides), dev = _dev_parts(where, parts)
+        (ptrs, rows, cols, strides, *lay), dev = _dev_parts(where, parts, layouts)
         live = [int(r) for r, c in zip(rows, cols) if c]
         if len(set(live)) != len(live):
             raise ValueError("%s: the heights of one call must be distinct, got %r" % (where, rows.tolist()))
         if len(set(live) | set(self._heights)) > _lib.MMCS_MAX_GROUPS:
             raise ValueError("%s: at most %d distinct heights" % (where, _lib.MMCS_MAX_GROUPS))
-        _dev_call(where, dev, "hades252_dmmcs_absorb", h, _ptr(ptrs), _ptr(rows), _ptr(cols), _ptr(strides), len(parts))
+        if lay:
+            _dev_call(where, dev, "hades252_rmmcs_absorb_ex", h, _ptr(ptrs), _ptr(rows), _ptr(cols), _ptr(strides), _ptr(lay[0]), len(parts))
+        else:
+            _dev_call(where, dev, "hades252_dmmcs_absorb", h, _ptr(ptrs), _ptr(rows), _ptr(cols), _ptr(strides), len(parts))
         self._heights += [r for r in live if r not in self._heights]
         return self
 
@@ -1566,13 +1622,14 @@ class Mmcs:
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         return torch.as_tensor(_DeviceWords(ptr.value, n_bytes.value // 32), device=dev).clone(), int(arity.value)
 
-    def open_dev(self, parts, indices_t):
+    def open_dev(self, parts, indices_t, layouts=None):
         """``hades252_dmmcs_open``: (rows int64 [q, sum of the parts' columns, 4], paths int64 [q, depth, arity - 1, 4]) of the
         indices ``indices_t`` (CUDA int64 [q]) from the committed matrices ``parts`` (as absorb_dev takes them, tallest
-        first) and the tree of the last commit: what mmcs_verify_dev reads.  An index >= the tallest height gives zeros."""
+        first) and the tree of the last commit: what mmcs_verify_dev reads.  An index >= the tallest height gives zeros.
+        With ``layouts`` (``hades252_rmmcs_open_ex``) a LAYOUT_ROWS part is a row-major matrix, as in absorb_dev."""
         where = "Mmcs.open_dev"
         h = self._handle(where)
-        (ptrs, rows, cols, strides), dev = _dev_parts(where, parts)
+        (ptrs, rows, cols, strides, *lay), dev = _dev_parts(where, parts, layouts)
         iptr, q, idev = _dev_buffer(indices_t, 8, where)
         _same_device(where, dev, idev)
         if indices_t.dim() != 1 or indices_t.element_size() != 8:
@@ -1585,8 +1642,12 @@ class Mmcs:
         depth = _mmcs_depth(where, hs[0], int(arity.value))
         out_rows = _dev_empty(dev, q, int(cols.sum()), 4)
         paths = _dev_empty(dev, q, depth, int(arity.value) - 1, 4)
-        _dev_call(where, dev, "hades252_dmmcs_open", h, _ptr(ptrs), _ptr(rows), _ptr(cols), _ptr(strides), len(parts), iptr, q,
-                  out_rows.data_ptr(), paths.data_ptr())
+        if lay:
+            _dev_call(where, dev, "hades252_rmmcs_open_ex", h, _ptr(ptrs), _ptr(rows), _ptr(cols), _ptr(strides), _ptr(lay[0]),
+                      len(parts), iptr, q, out_rows.data_ptr(), paths.data_ptr())
+        else:
+            _dev_call(where, dev, "hades252_dmmcs_open", h, _ptr(ptrs), _ptr(rows), _ptr(cols), _ptr(strides), len(parts), iptr, q,
+                      out_rows.data_ptr(), paths.data_ptr())
         return out_rows, paths
 
     def close(self) -> None:

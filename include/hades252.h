@@ -886,6 +886,62 @@ int hades252_dmmcs_verify(const void *d_rows, const uint64_t *heights, const uin
                           const uint64_t capacity_mont[4], int pad_mode, const uint64_t tag_mont[4],
                           const uint64_t inject_tag_mont[4], int out_idx, void *d_roots, void *stream);
 
+/* ---- row-major matrices for mixed-height commitments, host and device (f16) ---- CONVENTION UNPINNED
+ * The commitments of f14 / f15, above, for a prover that keeps its matrices ROW by row (a trace is an array of rows, an opened
+ * row a contiguous slice): the same handle (hades252_mmcs_new), groups, commit, tree, paths and verification, with no
+ * transpose anywhere.  A ROW-MAJOR PART is an n_rows x n_cols matrix whose scalar (r, j) is at base + (r * stride + j) * 32
+ * bytes, stride >= n_cols counted in scalars, every scalar four Montgomery limbs, fully reduced and not checked, as
+ * everywhere.  Absorbing it into the group of height n_rows is DEFINED as absorbing the column-major matrix with the same
+ * entries by the rules of hades252_mmcs_absorb: the handle then holds, byte for byte, the states it would hold after
+ * hades252_mmcs_absorb / hades252_dmmcs_absorb of the transposed matrix, so commit, tree, paths, verification and roots are
+ * what they were.  The group is created at first use, the open block position is the group's column total mod 4, and calls in
+ * either layout, host and device, mix freely on one handle and one group (under the ordering rule of f15).  The family is
+ * hades252_rmmcs_* ("r" for row-major, as f15's "d" is for device-resident): the hades252_mmcs_* and hades252_dmmcs_*
+ * families stay exactly the calls of f14 and f15.
+ *   HADES252_LAYOUT_COLS     column-major: strides[p] is the plane stride (rows per plane), scalar (r, j) at
+ *                            d_mats[p] + (j * strides[p] + r) * 32.
+ *   HADES252_LAYOUT_ROWS     row-major: strides[p] is the row stride (scalars per row).
+ *   hades252_rmmcs_absorb_rows  the host form: the next n_cols columns of the group of height n_rows from a row-major matrix
+ *                            in HOST memory, by the rules of hades252_mmcs_absorb.  Synchronous: the caller may reuse rows
+ *                            when it returns.  The matrix travels in tiles of K rows x G columns through two device
+ *                            buffers, tile t + 1 copied while tile t is absorbed, K and G as in hades252_matstream_absorb
+ *                            (K = all rows up to 2^18, G = 128 MiB / (32 K) columns, a multiple of four): one pitched 2-D
+ *                            copy per tile (source pitch row_stride * 32, width G * 32, height K), which is one contiguous
+ *                            copy when a tile holds whole rows and row_stride = n_cols.  The tile lands row-major on the
+ *                            device and is absorbed as it lies.  Page-locked rows are recommended, as for f12.
+ *                            hades252_mmcs_open needs no twin: the caller gathers its own rows.
+ *   hades252_rmmcs_absorb_ex hades252_dmmcs_absorb in every rule, with a layout per part: layouts is a HOST array, not
+ *                            referenced after the call returns; layouts = NULL means every part is column-major, and the
+ *                            handle is then left byte-identical to hades252_dmmcs_absorb with the same arguments.  All
+ *                            parts of a call still run as ONE launch, whatever their layouts, shortest part first.  A part
+ *                            with n_cols[p] = 0 is skipped whatever else it holds, its layout included.
+ *   hades252_rmmcs_open_ex   hades252_dmmcs_open with a layout per committed matrix: d_rows and d_paths are what
+ *                            hades252_dmmcs_open writes for the column-major twins.  An index >= h_0 gives an all-zero row
+ *                            and an all-zero path: nothing outside the matrices and the tree is read.  Two launches: the
+ *                            row gather -- one lane per (query, column) in output order, so for a row-major matrix
+ *                            consecutive lanes read and write consecutive scalars -- and ONE call of
+ *                            hades252_merkle_open_dev.
+ * hades252_dmmcs_absorb and hades252_dmmcs_open are untouched and keep their own kernels; the _ex forms run one kernel
+ * each that addresses a matrix through a row step and a column step the host computes from the layout.
+ * Rules, all decided before the device is touched; a refused call allocates nothing and leaves the handle exactly as it
+ * was.  The rules of hades252_dmmcs_absorb / hades252_dmmcs_open hold for the _ex forms (a NULL handle or array -- layouts
+ * aside --, n_parts outside 1 .. 32, heights, alignment: device pointers are 16-byte aligned), and for a part that is not
+ * skipped each of: a layout other than 0 or 1, a row-major strides[p] < n_cols[p] (column-major: strides[p] < n_rows[p]),
+ * a byte count n_rows * stride * 32 (column-major: n_cols * stride * 32) that overflows size_t is
+ * HADES252_ERR_INVALID_ARG.  absorb_rows: n_cols = 0 is a no-op success, even with NULL rows, and creates nothing; n_rows
+ * outside 1 .. 2^30, NULL rows or rows that are not 8-byte aligned, row_stride < n_cols, a byte count that overflows
+ * size_t, a column total that overflows uint64_t or a 33rd distinct height is HADES252_ERR_INVALID_ARG.  A HIP failure
+ * inside a call returns HADES252_ERR_HIP and poisons the handle, as in f14 / f15.
+ * No row-major form of f12 / f13 on their own (one group of a commitment is that stream), no witness form, no multiproofs. */
+#define HADES252_LAYOUT_COLS 0   /* column-major: strides[p] is the plane stride (rows per plane) */
+#define HADES252_LAYOUT_ROWS 1   /* row-major:    strides[p] is the row stride (scalars per row) */
+int hades252_rmmcs_absorb_rows(void *mc, const uint64_t *rows, size_t n_rows, size_t n_cols, size_t row_stride);
+int hades252_rmmcs_absorb_ex(void *mc, const void *const *d_mats, const uint64_t *n_rows, const uint64_t *n_cols,
+                             const uint64_t *strides, const uint32_t *layouts, size_t n_parts, void *stream);
+int hades252_rmmcs_open_ex(const void *mc, const void *const *d_mats, const uint64_t *n_rows, const uint64_t *n_cols,
+                           const uint64_t *strides, const uint32_t *layouts, size_t n_parts,
+                           const uint64_t *d_indices, size_t n_queries, void *d_rows, void *d_paths, void *stream);
+
 /* ---- synthetic inputs and digests (benchmark / verification plumbing) --------------------- */
 /* Generator B: scalar e (global element index first_elem + k) gets 4 splitmix64 limbs, top limb
  * masked to 62 bits (always < p); see DESIGN.md.  Stateless, so shards generate independently. */

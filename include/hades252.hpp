@@ -413,6 +413,24 @@ public:
         check(hades252_dmmcs_open(h_, d_planes, n_rows, n_cols, plane_strides, n_parts, d_indices, n_queries, d_rows, d_paths,
                                   stream), "Mmcs::open_dev");
     }
+    // ROW-major matrices (include/hades252.h, f16): scalar (r, j) = rows[r * row_stride + j], absorbed as the column-major
+    // matrix with the same entries would be -- no transpose anywhere.  Host memory, synchronous.
+    void absorb_rows(const BlsScalar *rows, std::size_t n_rows, std::size_t n_cols, std::size_t row_stride) {
+        check(hades252_rmmcs_absorb_rows(h_, reinterpret_cast<const std::uint64_t *>(rows), n_rows, n_cols, row_stride),
+              "Mmcs::absorb_rows");
+    }
+    // absorb_dev / open_dev with a layout per matrix (HADES252_LAYOUT_COLS / HADES252_LAYOUT_ROWS, a host array; nullptr:
+    // all column-major): strides[p] is the plane stride or the row stride of matrix p
+    void absorb_dev(const void *const *d_mats, const std::uint64_t *n_rows, const std::uint64_t *n_cols,
+                    const std::uint64_t *strides, const std::uint32_t *layouts, std::size_t n_parts, void *stream = nullptr) {
+        check(hades252_rmmcs_absorb_ex(h_, d_mats, n_rows, n_cols, strides, layouts, n_parts, stream), "Mmcs::absorb_dev");
+    }
+    void open_dev(const void *const *d_mats, const std::uint64_t *n_rows, const std::uint64_t *n_cols,
+                  const std::uint64_t *strides, const std::uint32_t *layouts, std::size_t n_parts, const std::uint64_t *d_indices,
+                  std::size_t n_queries, void *d_rows, void *d_paths, void *stream = nullptr) const {
+        check(hades252_rmmcs_open_ex(h_, d_mats, n_rows, n_cols, strides, layouts, n_parts, d_indices, n_queries, d_rows, d_paths,
+                                     stream), "Mmcs::open_dev");
+    }
 };
 // mmcs_verify with rows, indices, paths and roots in DEVICE memory: one launch on `stream`
 inline void mmcs_verify_dev(const void *d_rows, const std::uint64_t *heights, const std::uint64_t *cols, std::size_t n_groups,
