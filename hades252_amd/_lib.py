@@ -33,6 +33,7 @@ GRIND_MAX_JOBS = 65535
 MATRIX_MAX_COLS = 4096
 MMCS_MAX_GROUPS = 32
 LAYOUT_COLS, LAYOUT_ROWS = 0, 1     # HADES252_LAYOUT_*: column-major / row-major matrices (f16)
+WMMCS_SPONGE, WMMCS_INJECT, WMMCS_CLIMB = 0, 1, 2     # HADES252_WMMCS_*: the step kinds of an opening's chain (f17)
 
 # every symbol include/hades252.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -194,6 +195,14 @@ SIGNATURES = {
     "hades252_rmmcs_absorb_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "hades252_rmmcs_open_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
                                        c_void_p, c_void_p, c_void_p]),
+    "hades252_wmmcs_perms": (c_size_t, [c_void_p, c_void_p, c_size_t, c_int, c_int]),
+    "hades252_wmmcs_steps": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p, c_size_t]),
+    "hades252_wmmcs_inputs": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int,
+                                      POINTER(c_uint64), c_int, POINTER(c_uint64), POINTER(c_uint64), c_int, c_void_p, c_void_p,
+                                      c_void_p]),
+    "hades252_wmmcs_witness": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int,
+                                       POINTER(c_uint64), c_int, POINTER(c_uint64), POINTER(c_uint64), c_int, c_void_p, c_void_p,
+                                       c_void_p, c_void_p]),
     "hades252_gen_b_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_uint64, c_void_p]),
     "hades252_gen_a_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_void_p]),
     "hades252_digest_dev": (c_int, [c_void_p, c_uint64, c_size_t, c_void_p, c_void_p]),

@@ -69,7 +69,12 @@ DMMCS_DEPS = ["kernels_dmmcs.hpp", "abi_dmmcs.hpp"]
 # (DEPS), outside device_source_hash and perm_fast_hash.  The host simulation runs the kernels from a driver of its own
 # (tests/hostsim_rowmajor).
 ROWMAJOR_DEPS = ["kernels_rowmajor.hpp", "abi_rowmajor.hpp", "host_rowmajor.hpp"]
-DEPS = HOST_DEPS + LAUNCH_POLICY_DEPS + DEVICE_DEPS + UNRECORDED_KERNEL_DEPS + GRIND_DEPS + INVERSE_DEPS + MATRIX_DEPS + MATRIX_STREAM_DEPS + MMCS_DEPS + DMMCS_DEPS + ROWMAJOR_DEPS + [os.path.join("..", "..", "include", "hades252.h")]
+# gadget witnesses of the openings of the commitments of MMCS_DEPS (the input state of every permutation of a verification's
+# chain, then the wires of k_perm_witness): one kernel and its host calls.  As DMMCS_DEPS: rebuilt like every other source
+# (DEPS), outside device_source_hash and perm_fast_hash.  The host simulation runs the kernel from a driver of its own
+# (tests/hostsim_wmmcs).
+WMMCS_DEPS = ["kernels_wmmcs.hpp", "abi_wmmcs.hpp"]
+DEPS = HOST_DEPS + LAUNCH_POLICY_DEPS + DEVICE_DEPS + UNRECORDED_KERNEL_DEPS + GRIND_DEPS + INVERSE_DEPS + MATRIX_DEPS + MATRIX_STREAM_DEPS + MMCS_DEPS + DMMCS_DEPS + ROWMAJOR_DEPS + WMMCS_DEPS + [os.path.join("..", "..", "include", "hades252.h")]
 # what the dominant kernel (k_perm_fast) is made of: profiles recorded for it stay valid while these are unchanged
 PERM_FAST_DEPS = ["fr32.hpp", "staging.hpp", "hades_fast.hpp", "k_perm_fast.hpp"]
 # ... plus these tables of hades_constants.inc (other kernels' tables may change without touching k_perm_fast)

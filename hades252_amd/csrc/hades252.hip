@@ -41,6 +41,7 @@ using namespace hades;
 #include "kernels_mmcs.hpp"
 #include "kernels_dmmcs.hpp"
 #include "kernels_rowmajor.hpp"
+#include "kernels_wmmcs.hpp"
 #include "kernels_witness.hpp"
 #include "kernels_aux.hpp"
 
@@ -70,4 +71,5 @@ using namespace hades;
 #include "abi_dmmcs.hpp"
 #include "abi_rowmajor.hpp"
 #include "host_rowmajor.hpp"
+#include "abi_wmmcs.hpp"
 #include "host_cipher.hpp"

@@ -1456,12 +1456,9 @@ def _dev_parts(where: str, parts, layouts=None):
     return arrays, got[0][4]
 
 
-def mmcs_verify_dev(rows_t, heights, cols, indices_t, paths_t, arity: int, capacity_mont: int, tag_mont: int,
-                    inject_tag_mont: int, pad_mode: int = 1, out_idx: int = 1):
-    """``hades252_dmmcs_verify``: mmcs_verify on DEVICE tensors, one launch on the current stream: ``rows_t`` int64
-    [q, sum(cols), 4], ``indices_t`` int64 [q], ``paths_t`` int64 [q, depth, arity - 1, 4] (what Mmcs.open_dev returns);
-    ``heights`` / ``cols`` stay host sequences.  -> roots int64 [q, 4] on that device; nothing is synchronised."""
-    where = "mmcs_verify_dev"
+def _mmcs_openings_dev(where: str, rows_t, heights, cols, indices_t, paths_t, arity, pad_mode, out_idx):
+    """The openings of a batch on DEVICE tensors, checked without the library: -> (the first eight arguments of
+    hades252_dmmcs_verify and its witness forms -- rows up to arity --, q, device, the (heights, cols) arrays they point to)."""
     rptr, n_row_scalars, dev = _dev_buffer(rows_t, 32, where)
     pptr, _, pdev = _dev_buffer(paths_t, 32, where)
     iptr, q, idev = _dev_buffer(indices_t, 8, where)
@@ -1476,10 +1473,69 @@ def mmcs_verify_dev(rows_t, heights, cols, indices_t, paths_t, arity: int, capac
     if indices_t.dim() != 1 or indices_t.element_size() != 8:
         raise ValueError("%s: indices must be %d 8-byte words" % (where, q))
     _matrix_modes(where, pad_mode, out_idx)
+    return (rptr, _ptr(hs), _ptr(cs), hs.size, iptr, pptr, q, arity), q, dev, (hs, cs)
+
+
+def mmcs_verify_dev(rows_t, heights, cols, indices_t, paths_t, arity: int, capacity_mont: int, tag_mont: int,
+                    inject_tag_mont: int, pad_mode: int = 1, out_idx: int = 1):
+    """``hades252_dmmcs_verify``: mmcs_verify on DEVICE tensors, one launch on the current stream: ``rows_t`` int64
+    [q, sum(cols), 4], ``indices_t`` int64 [q], ``paths_t`` int64 [q, depth, arity - 1, 4] (what Mmcs.open_dev returns);
+    ``heights`` / ``cols`` stay host sequences.  -> roots int64 [q, 4] on that device; nothing is synchronised."""
+    where = "mmcs_verify_dev"
+    front, q, dev, _keep = _mmcs_openings_dev(where, rows_t, heights, cols, indices_t, paths_t, arity, pad_mode, out_idx)
     roots = _dev_empty(dev, q, 4)
-    _dev_call(where, dev, "hades252_dmmcs_verify", rptr, _ptr(hs), _ptr(cs), hs.size, iptr, pptr, q, arity,
-              _tag_arr(capacity_mont), pad_mode, _tag_arr(tag_mont), _tag_arr(inject_tag_mont), out_idx, roots.data_ptr())
+    _dev_call(where, dev, "hades252_dmmcs_verify", *front, _tag_arr(capacity_mont), pad_mode, _tag_arr(tag_mont),
+              _tag_arr(inject_tag_mont), out_idx, roots.data_ptr())
     return roots
+
+
+def mmcs_perms(heights, cols, arity: int, pad_mode: int = 1) -> int:
+    """``hades252_wmmcs_perms``: permutations of one opening's chain -- the groups' sponge blocks, the levels and the
+    injections -- for the shape ``mmcs_verify`` takes."""
+    where = "mmcs_perms"
+    hs, cs, _ = _mmcs_groups(where, heights, cols, arity)
+    _matrix_modes(where, pad_mode)
+    return int(_lib.lib().hades252_wmmcs_perms(_ptr(hs), _ptr(cs), hs.size, arity, pad_mode))
+
+
+def mmcs_steps(heights, cols, arity: int, pad_mode: int = 1) -> np.ndarray:
+    """``hades252_wmmcs_steps``: the chain of one opening as data, uint32 [P, 3]: (kind, group, ordinal) of every step, kind
+    one of _lib.WMMCS_SPONGE / WMMCS_INJECT / WMMCS_CLIMB, ordinal the block of the group's row, the child level counted from
+    the leaves, or 0 for an injection."""
+    where = "mmcs_steps"
+    hs, cs, _ = _mmcs_groups(where, heights, cols, arity)
+    _matrix_modes(where, pad_mode)
+    steps = np.zeros((mmcs_perms(hs, cs, arity, pad_mode), 3), dtype=np.uint32)
+    check(_lib.lib().hades252_wmmcs_steps(_ptr(hs), _ptr(cs), hs.size, arity, pad_mode, _ptr(steps), steps.shape[0]), where)
+    return steps
+
+
+def mmcs_inputs_dev(rows_t, heights, cols, indices_t, paths_t, arity: int, capacity_mont: int, tag_mont: int,
+                    inject_tag_mont: int, pad_mode: int = 1, out_idx: int = 1):
+    """``hades252_wmmcs_inputs``: the state that enters every permutation of the chains mmcs_verify_dev walks, one launch on
+    the current stream; the arguments are mmcs_verify_dev's.  -> (inputs int64 [P, q, 5, 4], roots int64 [q, 4]) with P =
+    mmcs_perms(...): inputs[t, i] enters step t of opening i, roots are mmcs_verify_dev's."""
+    where = "mmcs_inputs_dev"
+    front, q, dev, (hs, cs) = _mmcs_openings_dev(where, rows_t, heights, cols, indices_t, paths_t, arity, pad_mode, out_idx)
+    inputs = _dev_empty(dev, mmcs_perms(hs, cs, arity, pad_mode), q, WIDTH, 4)
+    roots = _dev_empty(dev, q, 4)
+    _dev_call(where, dev, "hades252_wmmcs_inputs", *front, _tag_arr(capacity_mont), pad_mode, _tag_arr(tag_mont),
+              _tag_arr(inject_tag_mont), out_idx, inputs.data_ptr(), roots.data_ptr())
+    return inputs, roots
+
+
+def mmcs_witness_dev(rows_t, heights, cols, indices_t, paths_t, arity: int, capacity_mont: int, tag_mont: int,
+                     inject_tag_mont: int, pad_mode: int = 1, out_idx: int = 1):
+    """``hades252_wmmcs_witness``: gadget witness of the openings mmcs_verify_dev verifies.  -> (wires int64 [972, P, q, 4],
+    inputs int64 [P, q, 5, 4], roots int64 [q, 4]): wires.reshape(972, P * q, 4) == perm_witness(inputs) byte for byte, and
+    r2[out_idx] of the last step's records is the roots."""
+    where = "mmcs_witness_dev"
+    front, q, dev, (hs, cs) = _mmcs_openings_dev(where, rows_t, heights, cols, indices_t, paths_t, arity, pad_mode, out_idx)
+    wires, inputs = _witness_pair(dev, mmcs_perms(hs, cs, arity, pad_mode), q)
+    roots = _dev_empty(dev, q, 4)
+    _dev_call(where, dev, "hades252_wmmcs_witness", *front, _tag_arr(capacity_mont), pad_mode, _tag_arr(tag_mont),
+              _tag_arr(inject_tag_mont), out_idx, inputs.data_ptr(), wires.data_ptr(), roots.data_ptr())
+    return wires, inputs, roots
 
 
 class _DeviceWords:

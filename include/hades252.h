@@ -942,6 +942,75 @@ int hades252_rmmcs_open_ex(const void *mc, const void *const *d_mats, const uint
                            const uint64_t *strides, const uint32_t *layouts, size_t n_parts,
                            const uint64_t *d_indices, size_t n_queries, void *d_rows, void *d_paths, void *stream);
 
+/* ---- gadget witnesses of mixed-height commitment openings (f17): the fifth chain of row f4 ---- CONVENTION UNPINNED
+ * What hades252_sponge_witness_dev and friends are for their chains, for an opening of a commitment of f14 / f15 / f16: the
+ * chain a recursive verifier hashes most -- per query every group's row sponge, the injections and the path.  The family is
+ * hades252_wmmcs_* ("w" for witness); the blocks of f14 to f16 stay true of their own calls.  Everything is in DEVICE
+ * memory, on the caller's stream: the calls enqueue there and return; nothing is synchronised and nothing is downloaded.
+ * The conventions are those of f14 (capacity, padding, the two tags: parameters, still unpinned), the shape arguments those
+ * of hades252_dmmcs_verify with the same rules: heights and cols are HOST arrays, d_rows is query-major with the groups
+ * concatenated tallest first, d_indices and d_paths as hades252_dmmcs_open writes them.  Scalars are four Montgomery limbs,
+ * fully reduced and not checked, as everywhere.
+ * One opening costs P = hades252_sponge_blocks(cols[g], pad_mode) summed over the groups + D + (G - 1) permutations, in the
+ * order k_mmcs_verify walks them: group 0's blocks; the levels up to group 1's height; group 1's blocks; its injection; the
+ * levels up to group 2's height; and so on up to the root.  A batch of n openings is P * n permutations, numbered
+ * rec = t * n + q (step-major, query within the step, as in the sibling chain witnesses).  The state that enters step t of
+ * query q:
+ *   sponge, block 0 of a group's row   [capacity, v0, v1, v2, v3]: v_k is column k of the row; under pad_mode 1 a single 1
+ *                                      sits in position cols[g]; zeros follow.
+ *   sponge, block b > 0                the previous permutation's output with block b added into words 1..4 (the absorb add
+ *                                      gates' outputs).
+ *   inject                             [inject_tag, node, digest, 0, 0]: digest is word 1 of the previous permutation's output
+ *                                      (the group's last block), node is word out_idx of the output of the last climb step
+ *                                      before the group's sponge.
+ *   climb                              [tag, the arity children, 0 ...]: the node sits at child position
+ *                                      (index / arity^level) % arity with the level's arity - 1 siblings from d_paths around
+ *                                      it, exactly as k_mmcs_verify places them.  The node is word out_idx of the last climb
+ *                                      or inject output; for the first climb it is word 1 of group 0's last sponge output.
+ * Indices are not range-checked, as in verify.  The gadget's selection, add and copy constraints (where the node sits, the
+ * block added into words 1..4, the links between a record's input words and earlier records' outputs) are the consumer's: the
+ * inputs carry their values, hades252_wmmcs_steps says which constraint belongs to which step.
+ *   hades252_wmmcs_perms    P, or 0 for a shape hades252_mmcs_verify would refuse.  Pure host code.
+ *   hades252_wmmcs_steps    the walk as data: steps[3 t ..] = (kind, group, ordinal) of step t, kind one of
+ *                           HADES252_WMMCS_SPONGE / _INJECT / _CLIMB, ordinal the block number within the group's row, the
+ *                           child level counted from the leaves (0 .. D - 1), or 0 for an injection; the group of a climb
+ *                           step is the last group whose row has been hashed.  n_steps other than P is
+ *                           HADES252_ERR_INVALID_ARG.  Pure host code, from the same closed-form count the launch uses.
+ *   hades252_wmmcs_inputs   d_inputs receives P * n states of 160 B (the AoS format of the perm entry points) at rec * 160;
+ *                           d_roots (may be NULL) receives n roots, byte for byte those of hades252_dmmcs_verify.  ONE launch
+ *                           of k_mmcs_inputs: one query per lane, the walk of k_mmcs_verify with the five words stored in
+ *                           front of every permutation.  Useful on its own: the inputs feed hades252_perm_witness_dev,
+ *                           hades252_perm_trace_dev or hades252_perm_trace_scaled_dev, whichever form the circuit takes.
+ *   hades252_wmmcs_witness  the inputs stage, then hades252_perm_witness_dev(d_inputs, d_wires, P * n, stream) on the same
+ *                           stream: d_wires receives 972 * P * n scalars, wire-major.  Defining property, as for the sibling
+ *                           chains: wires == hades252_perm_witness_dev(inputs) byte for byte, the P * n states taken as one
+ *                           flat batch -- here by construction.  r2[out_idx] of the last step's record is the root.  NOT a
+ *                           fused kernel: the chain is computed twice, once at the rate of the verification and once by the
+ *                           witness kernel over independent records.  Measured (profiles/f17_mmcs_witness): 2^15 openings of
+ *                           26 permutations take 1.80 x hades252_perm_witness_dev on the same records and 1.003 x the sum of
+ *                           the two stages; the inputs stage of 2^18 openings takes 1.008 x hades252_dmmcs_verify.
+ * Rules, all decided before the device is touched.  Those of hades252_dmmcs_verify (d_roots aside: it may be NULL, and is
+ * 16-byte aligned if not); n_queries = 0 is a no-op success, even with NULL pointers; d_inputs must be non-NULL and 16-byte
+ * aligned, and for the witness call d_wires too; P * n_queries above 2^30 is HADES252_ERR_INVALID_ARG; steps: a NULL or
+ * misaligned steps, a refused shape.  A failed launch is HADES252_ERR_HIP with the thread's last HIP error set; there is no
+ * handle to poison.
+ * No one-opening-per-wave latency form, no fused kernel, no multiproofs. */
+#define HADES252_WMMCS_SPONGE 0   /* a block of a group's row sponge */
+#define HADES252_WMMCS_INJECT 1   /* the injection of a shorter group's row digest */
+#define HADES252_WMMCS_CLIMB 2    /* a tree level */
+size_t hades252_wmmcs_perms(const uint64_t *heights, const uint64_t *cols, size_t n_groups, int arity, int pad_mode);
+int hades252_wmmcs_steps(const uint64_t *heights, const uint64_t *cols, size_t n_groups, int arity, int pad_mode,
+                         uint32_t *steps, size_t n_steps);
+int hades252_wmmcs_inputs(const void *d_rows, const uint64_t *heights, const uint64_t *cols, size_t n_groups,
+                          const uint64_t *d_indices, const void *d_paths, size_t n_queries, int arity,
+                          const uint64_t capacity_mont[4], int pad_mode, const uint64_t tag_mont[4],
+                          const uint64_t inject_tag_mont[4], int out_idx, void *d_inputs, void *d_roots, void *stream);
+int hades252_wmmcs_witness(const void *d_rows, const uint64_t *heights, const uint64_t *cols, size_t n_groups,
+                           const uint64_t *d_indices, const void *d_paths, size_t n_queries, int arity,
+                           const uint64_t capacity_mont[4], int pad_mode, const uint64_t tag_mont[4],
+                           const uint64_t inject_tag_mont[4], int out_idx, void *d_inputs, void *d_wires, void *d_roots,
+                           void *stream);
+
 /* ---- synthetic inputs and digests (benchmark / verification plumbing) --------------------- */
 /* Generator B: scalar e (global element index first_elem + k) gets 4 splitmix64 limbs, top limb
  * masked to 62 bits (always < p); see DESIGN.md.  Stateless, so shards generate independently. */

@@ -441,6 +441,33 @@ inline void mmcs_verify_dev(const void *d_rows, const std::uint64_t *heights, co
                                 pad_one ? 1 : 0, tag.limbs, inject_tag.limbs, out_idx, d_roots, stream),
           "mmcs_verify_dev");
 }
+// gadget witnesses of those openings (include/hades252.h, f17).  mmcs_perms: the permutations P of one opening's chain, 0
+// for a refused shape; mmcs_steps: the chain as (kind, group, ordinal) triples, steps[3 t ..] for step t
+inline std::size_t mmcs_perms(const std::uint64_t *heights, const std::uint64_t *cols, std::size_t n_groups, int arity, bool pad_one) {
+    return hades252_wmmcs_perms(heights, cols, n_groups, arity, pad_one ? 1 : 0);
+}
+inline void mmcs_steps(const std::uint64_t *heights, const std::uint64_t *cols, std::size_t n_groups, int arity, bool pad_one,
+                       std::uint32_t *steps, std::size_t n_steps) {
+    check(hades252_wmmcs_steps(heights, cols, n_groups, arity, pad_one ? 1 : 0, steps, n_steps), "mmcs_steps");
+}
+// d_inputs: P * n_queries states of 160 B, record t * n_queries + q enters step t of opening q; d_roots may be nullptr
+inline void mmcs_inputs_dev(const void *d_rows, const std::uint64_t *heights, const std::uint64_t *cols, std::size_t n_groups,
+                            const std::uint64_t *d_indices, const void *d_paths, std::size_t n_queries, int arity,
+                            const BlsScalar &capacity, bool pad_one, const BlsScalar &tag, const BlsScalar &inject_tag, int out_idx,
+                            void *d_inputs, void *d_roots = nullptr, void *stream = nullptr) {
+    check(hades252_wmmcs_inputs(d_rows, heights, cols, n_groups, d_indices, d_paths, n_queries, arity, capacity.limbs,
+                                pad_one ? 1 : 0, tag.limbs, inject_tag.limbs, out_idx, d_inputs, d_roots, stream),
+          "mmcs_inputs_dev");
+}
+// ... and d_wires: 972 * P * n_queries scalars, wire-major, exactly perm_witness of d_inputs
+inline void mmcs_witness_dev(const void *d_rows, const std::uint64_t *heights, const std::uint64_t *cols, std::size_t n_groups,
+                             const std::uint64_t *d_indices, const void *d_paths, std::size_t n_queries, int arity,
+                             const BlsScalar &capacity, bool pad_one, const BlsScalar &tag, const BlsScalar &inject_tag, int out_idx,
+                             void *d_inputs, void *d_wires, void *d_roots = nullptr, void *stream = nullptr) {
+    check(hades252_wmmcs_witness(d_rows, heights, cols, n_groups, d_indices, d_paths, n_queries, arity, capacity.limbs,
+                                 pad_one ? 1 : 0, tag.limbs, inject_tag.limbs, out_idx, d_inputs, d_wires, d_roots, stream),
+          "mmcs_witness_dev");
+}
 inline std::size_t mmcs_tree_bytes(std::size_t max_rows, int arity) { return hades252_mmcs_tree_bytes(max_rows, arity); }
 inline void mmcs_open(const BlsScalar *tree, std::size_t max_rows, int arity, const std::uint64_t *indices, std::size_t n_queries,
                       BlsScalar *paths_out) {
